@@ -131,9 +131,24 @@ def _cached(path, make, cache=True):
     return obj
 
 
+def generator_digest():
+    """Digest of everything a synthetic field is made from: the package's Python sources and the library whose host
+    spline prefilter renders the images.  It names the pickled field, so that a field another version of the code made
+    is never reused."""
+    import hashlib
+    from celeste_jl_amd import cabi
+    h = hashlib.sha256()
+    pkg = os.path.join(ROOT, "celeste.jl_amd")
+    for path in [os.path.join(pkg, f) for f in sorted(os.listdir(pkg)) if f.endswith((".py", ".json"))] + \
+            [os.environ.get("CELESTE_MI355X_LIB") or cabi.LIB_PATH]:
+        with open(path, "rb") as f:
+            h.update(f.read())
+    return h.hexdigest()[:16]
+
+
 def build_field(H, W, n_sources, seed, cache=True, variable=False):
     from celeste_jl_amd import synthetic
-    return _cached("/tmp/celeste_field_%d_%d_%d_%d%s.pkl" % (H, W, n_sources, seed, "_var" if variable else ""),
+    return _cached("/tmp/celeste_field_%d_%d_%d_%d%s_%s.pkl" % (H, W, n_sources, seed, "_var" if variable else "", generator_digest()),
                    lambda: synthetic.make_field(H, W, n_sources, seed=seed, variable=variable,
                                                 name="synthetic_%dx%dx5_%dsrc%s" % (H, W, n_sources, "_variable" if variable else "")), cache)
 
@@ -144,6 +159,27 @@ def build_multifield(grid, H, W, n_sources, seed, cache=True):
     # (not pickled: 80 planes of 12 MB; generation takes ~15 s with 16 workers)
     return synthetic.make_multifield(grid=grid, H=H, W=W, overlap=0.10, n_sources=n_sources, seed=seed, sparse=True,
                                      workers=workers)
+
+
+DUMP_MAX_BYTES = 64_000_000
+
+
+def dump_outputs(out_dir, arrays, max_bytes=DUMP_MAX_BYTES, seed=0):
+    """--dump-outputs: every array of `arrays` (name -> per-source rows) as <out_dir>/<name>.npy, float32 / float64.  When
+    the arrays exceed `max_bytes` together, every array keeps the same fraction of its rows, drawn with a fixed seed (an
+    array's row count alone decides which rows), and <name>_rows.npy holds the row numbers that were kept."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {k: np.asarray(a) for k, a in arrays.items()}
+    arrays = {k: a if a.dtype in (np.float32, np.float64) else a.astype(np.float64) for k, a in arrays.items()}
+    header = 128 * 2 * len(arrays)          # (.npy headers, both files of a sampled array)
+    total = sum(a.nbytes + 8 * len(a) for a in arrays.values())
+    frac = min(1.0, (max_bytes - header) / total)
+    for name, a in arrays.items():
+        if frac < 1.0:
+            rows = np.sort(np.random.default_rng(seed).choice(len(a), max(1, int(len(a) * frac)), replace=False))
+            a = a[rows]
+            np.save(os.path.join(out_dir, name + "_rows.npy"), rows.astype(np.float64))
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
 
 
 def usable_cores():
@@ -283,9 +319,16 @@ def main():
                     help="N > 1: do not let rank 0 repeat the sweep through celeste_group_* (the in-library driver) after the ranks' run")
     ap.add_argument("--check-dir", default=None,
                     help="every rank writes its gathered (v, d) of the last sweep to <dir>/rank<r>.npz (tests)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, rank 0 writes what the last timed sweep computed as DIR/<name>.npy (float64): "
+                         "v [S], d [S, 44] of every source, h [n, 44, 44] and cnt [n, 2] (pixel counters) of rank 0's shard and "
+                         "shard_targets [n], the source of each of those rows; at most 64 MB in all (a fixed, seeded sample of "
+                         "the rows beyond that, with DIR/<name>_rows.npy)")
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps is not None and args.steps < 1:
+        raise SystemExit("--steps must be >= 1")
     if args.driver == "group":
         if int(os.environ.get("RANK", "0")) != 0:
             return               # (started under a launcher: the group lives in ONE process -- rank 0's)
@@ -450,6 +493,9 @@ def main():
     if args.check_dir:
         os.makedirs(args.check_dir, exist_ok=True)
         np.savez(os.path.join(args.check_dir, "rank%d.npz" % rank), v=g_v, d=g_d, mine=mine, h=sweep.hessians())
+    if args.dump_outputs and rank == 0:
+        dumped = {"v": g_v, "d": g_d, "h": sweep.hessians(), "cnt": cnt_loc, "shard_targets": mine}
+        dump_outputs(args.dump_outputs, {k: a for k, a in dumped.items() if a is not None})
     pixel_visits_local = int(cnt_loc[:, 0].sum())
 
     # ---- dominant-kernel duration: HIP events recorded by the library on the launch stream, averaged ----
@@ -850,6 +896,8 @@ def group_measure(args, fld, devices, flags, check=True):
     if args.check_dir and check:
         os.makedirs(args.check_dir, exist_ok=True)
         np.savez(os.path.join(args.check_dir, "group.npz"), v=v, d=d)
+    if args.dump_outputs and check:      # (the group driver's sweep returns no Hessians: they stay on the members)
+        dump_outputs(args.dump_outputs, {"v": v, "d": d, "cnt": cnt})
     g.enable_timing(True)
     kms, ev_ms, ga_ms = [], [], []
     for _ in range(min(20, max(3, args.steps))):

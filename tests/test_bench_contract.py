@@ -4,6 +4,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -128,3 +129,57 @@ def test_bench_config5_mode_small_grid():
     chk = d["fp32_vs_fp64_device"]
     assert chk["sources_checked"] == 150 and max(chk["v"], chk["d"], chk["h"]) <= 1e-4
     assert d["roofline"]["kernel"] == "pixel_kernel<2, float>" and d["value"] > 0
+
+
+@pytest.mark.gpu
+def test_bench_dump_outputs(tmp_path):
+    """--dump-outputs DIR: what the last timed sweep computed, as float64 .npy files -- the same arrays as --check-dir writes in
+    the same run, and bit for bit the same in a second run with the same arguments (the inputs are seeded)"""
+    dumps = []
+    for run in range(2):
+        out_dir, chk = tmp_path / ("dump%d" % run), tmp_path / ("chk%d" % run)
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--height", "300", "--width", "260", "--sources", "60",
+                              "--steps", "4", "--warmup", "1", "--no-extras", "--no-cpu-baseline", "--no-live-pmc",
+                              "--dump-outputs", str(out_dir), "--check-dir", str(chk)],
+                             capture_output=True, text=True, timeout=600)
+        assert out.returncode == 0, out.stderr[-2000:]
+        d = json.loads([ln for ln in out.stdout.splitlines() if ln.strip()][-1])
+        assert d["steps"] == 4 and d["ms_per_step"] > 0
+        got = {p.stem: np.load(p) for p in out_dir.glob("*.npy")}
+        assert sorted(got) == ["cnt", "d", "h", "shard_targets", "v"]
+        assert all(a.dtype == np.float64 for a in got.values())
+        assert got["v"].shape == (60,) and got["d"].shape == (60, 44) and got["h"].shape == (60, 44, 44) and got["cnt"].shape == (60, 2)
+        ref = np.load(chk / "rank0.npz")
+        assert np.array_equal(got["v"], ref["v"]) and np.array_equal(got["d"], ref["d"]) and np.array_equal(got["h"], ref["h"])
+        assert np.array_equal(got["shard_targets"], ref["mine"]) and sorted(got["shard_targets"]) == list(range(60))
+        dumps.append(got)
+    for k in dumps[0]:
+        assert np.array_equal(dumps[0][k], dumps[1][k]), k
+
+
+def test_bench_dump_outputs_keeps_to_its_budget(tmp_path):
+    """beyond the byte budget every array keeps the same seeded fraction of its rows, and says which rows"""
+    sys.path.insert(0, ROOT)
+    import bench
+    rng = np.random.default_rng(1)
+    arrays = {"v": rng.random(500), "h": rng.random((500, 44, 44)), "cnt": np.arange(1000, dtype=np.int64).reshape(500, 2)}
+    bench.dump_outputs(str(tmp_path / "all"), arrays)
+    for k, a in arrays.items():
+        b = np.load(tmp_path / "all" / (k + ".npy"))
+        assert b.dtype in (np.float32, np.float64) and np.array_equal(b, a)
+    assert not list((tmp_path / "all").glob("*_rows.npy"))
+    budget = 1_000_000
+    for run in ("s1", "s2"):
+        bench.dump_outputs(str(tmp_path / run), arrays, max_bytes=budget)
+        assert sum(p.stat().st_size for p in (tmp_path / run).glob("*.npy")) <= budget
+    for k, a in arrays.items():
+        rows = np.load(tmp_path / "s1" / (k + "_rows.npy"))
+        b = np.load(tmp_path / "s1" / (k + ".npy"))
+        assert 0 < len(rows) < len(a) and rows.dtype == np.float64 and np.array_equal(b, a[rows.astype(np.int64)])
+        assert np.array_equal(b, np.load(tmp_path / "s2" / (k + ".npy")))
+    assert np.array_equal(np.load(tmp_path / "s1" / "v_rows.npy"), np.load(tmp_path / "s1" / "h_rows.npy"))
+
+
+def test_bench_refuses_fewer_than_one_step():
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], capture_output=True, text=True, timeout=600)
+    assert out.returncode != 0 and "--steps must be >= 1" in out.stderr and "{" not in out.stdout

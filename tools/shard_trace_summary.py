@@ -1,7 +1,8 @@
 """Summarise gpurun_out/shard/s_kernel_trace.csv (tools/shard_trace.sh): average duration per kernel and grid, and the
 timeline of one steady-state sweep per shard size."""
 import csv, collections, sys
-rows = list(csv.DictReader(open('/root/repo/gpurun_out/shard/s_kernel_trace.csv')))
+# usage: python tools/shard_trace_summary.py <s_kernel_trace.csv written by tools/shard_trace.sh>
+rows = list(csv.DictReader(open(sys.argv[1])))
 rows.sort(key=lambda r: int(r['Start_Timestamp']))
 agg = collections.defaultdict(list)
 for r in rows:
