@@ -2,7 +2,7 @@
 
 Import as ``celeste_jl_amd`` (see celeste_jl_amd.py at the repository root).
 """
-from . import cabi, params, model  # noqa: F401
+from . import cabi, params, model, detect  # noqa: F401
 from .params import (ids, CatalogEntry, generic_init_source, catalog_init_source, init_sources,  # noqa: F401
                      perturb_params)
 from .elbo import (ElboArgs, ElboConfig, SensitiveFloat, FieldContext, elbo, elbo_likelihood,  # noqa: F401

@@ -294,14 +294,19 @@ def group_joint_infer(group, catalog, target_sources: Sequence[int], neighbors: 
     return vp[targets]
 
 
-def infer_box(images, box: BoundingBox, catalog, method: str = "joint_vi", cfg: Optional[ElboConfig] = None,
+def infer_box(images, box: BoundingBox, catalog=None, method: str = "joint_vi", cfg: Optional[ElboConfig] = None,
               n_iters: int = NUM_JOINT_VI_ITERS, device: int = 0, schedule: str = "cyclades",
-              devices: Optional[Sequence[int]] = None) -> List[OptimizedSource]:
-    """infer_box / _infer_box (ParallelRun.jl:610-672) for a given catalog: patches for every catalog entry, targets
-    = entries strictly inside the box, neighbours may lie outside it, then joint or single variational inference
-    on the device.  (Source detection and MCMC are out of scope: `catalog` is required, method in {joint_vi, single_vi}.)
+              devices: Optional[Sequence[int]] = None, match_radius: float = 1.0 / 3600.0) -> List[OptimizedSource]:
+    """infer_box / _infer_box (ParallelRun.jl:610-672): targets = catalog entries strictly inside the box, neighbours
+    may lie outside it, then joint or single variational inference on the device (method in {joint_vi, single_vi};
+    MCMC is out of scope).  catalog=None: the catalog and the patches come from source detection on the device
+    (detect.detect_sources, detection.jl:39-171), as the reference's infer_box does without a catalog; otherwise
+    patches for every catalog entry (get_sky_patches).  match_radius: the world distance under which detections of
+    different images are one object (detection.jl's 1 arcsec; used only without a catalog).
     devices: HIP ordinals of a device group (celeste_group_*: one process, the reference's N workers = N devices, RCCL
     inside the library); None = the one `device`."""
+    if catalog is None:
+        return _infer_box_detected(images, box, method, cfg, n_iters, device, schedule, devices, match_radius)
     targets = [i for i, ce in enumerate(catalog) if box.contains(ce.pos)]
     if not targets:
         return []
@@ -339,5 +344,51 @@ def infer_box(images, box: BoundingBox, catalog, method: str = "joint_vi", cfg: 
     finally:
         ctx.close()
     flags = bad_sky_flags([catalog[t] for t in targets], images, device)
+    return [OptimizedSource(float(catalog[t].pos[0]), float(catalog[t].pos[1]), vs[k].copy(), flags[k], t in failed)
+            for k, t in enumerate(targets)]
+
+
+def _infer_box_detected(images, box: BoundingBox, method, cfg, n_iters, device, schedule, devices,
+                        match_radius) -> List[OptimizedSource]:
+    """_infer_box with the catalog and patches of detect_sources (ParallelRun.jl:661-665): targets strictly inside the
+    box, neighbours from the detection patches, the context (or device group) over those patches."""
+    from .detect import detect_sources
+    from .model import neighbor_map
+    catalog, patches = detect_sources(images, device=devices[0] if devices is not None else device,
+                                      match_radius=match_radius)
+    targets = [i for i, ce in enumerate(catalog) if box.contains(ce.pos)]
+    if not targets:
+        return []
+    neighbors = neighbor_map(patches)
+    failed: set = set()
+    if devices is not None:
+        from .group import FieldGroup
+        if schedule != "cyclades":
+            raise ValueError("a device group runs the reference's Cyclades schedule")
+        group = FieldGroup(images, patches, neighbors, devices=list(devices))
+        try:
+            if method == "joint_vi":
+                vs = group_joint_infer(group, catalog, targets, neighbors, cfg, n_iters=n_iters, failed=failed)
+            elif method == "single_vi":
+                vs = group_single_infer(group, catalog, targets, cfg, failed=failed)
+            else:
+                raise ValueError("unknown method: %s" % method)
+        finally:
+            group.close()
+        flag_device = devices[0]
+    else:
+        ctx = FieldContext(images, patches, neighbors, device=device)
+        try:
+            if method == "joint_vi":
+                vs = one_node_joint_infer(ctx, catalog, targets, neighbors, cfg, n_iters=n_iters, schedule=schedule,
+                                          failed=failed)
+            elif method == "single_vi":
+                vs = one_node_single_infer(ctx, catalog, targets, cfg, failed=failed)
+            else:
+                raise ValueError("unknown method: %s" % method)
+        finally:
+            ctx.close()
+        flag_device = device
+    flags = bad_sky_flags([catalog[t] for t in targets], images, flag_device)
     return [OptimizedSource(float(catalog[t].pos[0]), float(catalog[t].pos[1]), vs[k].copy(), flags[k], t in failed)
             for k, t in enumerate(targets)]
