@@ -23,7 +23,10 @@
 
 // Mutation testing (tests/test_mutants.py builds the library with -DCELESTE_MUTANT=k and checks that the parity
 // tests notice): 0 = the product; 1 = iota indexed by column instead of row; 2 = sky plane read transposed;
-// 3 = every patch uses stamp 0.  Never defined in the shipped build.
+// 3 = every patch uses stamp 0.  Single-precision code only (CELESTE_FLAG_FP32): 4 = galaxy_sums_px2's Hessian sums drop
+// the - hc p11 term of h4c; 5 = galaxy_sums_px2's gradient mode takes nu of the odd components from the even ones' half;
+// 6 = value_pixels_f2 takes p12 of the odd components from the even ones' half (neighbours' light); 7 = galaxy_sums_pk
+// forms h4b with -3 p11 instead of -3 p12.  Never defined in the shipped build.
 #ifndef CELESTE_MUTANT
 #define CELESTE_MUTANT 0
 #endif
@@ -1022,7 +1025,11 @@ __device__ __forceinline__ void value_pixels_f2(int lane, const DevPatch &P, con
                     f1 += w * (f2v){__builtin_amdgcn_exp2f(q2.x), __builtin_amdgcn_exp2f(q2.y)};
                 }
                 {
+#if CELESTE_MUTANT == 6
+                    const f2v p11 = k[0].yy, p12 = k[1].xx, p22 = k[2].yy, w = k[5].yy;
+#else
                     const f2v p11 = k[0].yy, p12 = k[1].yy, p22 = k[2].yy, w = k[5].yy;
+#endif
                     const f2v q2 = p11 * s11 + (p12 * s12 + p22 * s22);
                     f1 += w * (f2v){__builtin_amdgcn_exp2f(q2.x), __builtin_amdgcn_exp2f(q2.y)};
                 }
@@ -1614,8 +1621,13 @@ __device__ __forceinline__ typename TT::scalar galaxy_sums_pk(const CompR<float>
             S2a += ha * f; S2b += hb * f; S2c += hc * f;
             const f2v h3a = u * (ha - 2.0f * p11), h3b = v * ha + u * m2p12, h3c = u * hc + v * m2p12, h3d = v * (hc - 2.0f * p22);
             S3a += h3a * fn; S3b += h3b * fn; S3c += h3c * fn; S3d += h3d * fn;
+#if CELESTE_MUTANT == 7
+            const f2v h4a = u * h3a + ha * m3p11, h4b = v * h3a + ha * m3p11, h4c = u * h3c + (hb * m2p12 - hc * p11),
+                      h4d = u * h3d + hc * m3p12, h4e = v * h3d + hc * m3p22;
+#else
             const f2v h4a = u * h3a + ha * m3p11, h4b = v * h3a + ha * m3p12, h4c = u * h3c + (hb * m2p12 - hc * p11),
                       h4d = u * h3d + hc * m3p12, h4e = v * h3d + hc * m3p22;
+#endif
             S4a += h4a * fnn; S4b += h4b * fnn; S4c += h4c * fnn; S4d += h4d * fnn; S4e += h4e * fnn;
         };
         for (int c = 0; c < n_dev; c += 2) pair(c, U0);
@@ -1941,8 +1953,13 @@ __device__ __forceinline__ f2v galaxy_sums_px2(const f2v *tp, int n_dev, int nc,
             S2a += ha * f; S2b += hb * f; S2c += hc * f;
             const f2v h3a = u * (ha - 2.0f * p11), h3b = v * ha + u * m2p12, h3c = u * hc + v * m2p12, h3d = v * (hc - 2.0f * p22);
             S3a += h3a * fn; S3b += h3b * fn; S3c += h3c * fn; S3d += h3d * fn;
+#if CELESTE_MUTANT == 4
+            const f2v h4a = u * h3a + ha * m3p11, h4b = v * h3a + ha * m3p12, h4c = u * h3c + hb * m2p12,
+                      h4d = u * h3d + hc * m3p12, h4e = v * h3d + hc * m3p22;
+#else
             const f2v h4a = u * h3a + ha * m3p11, h4b = v * h3a + ha * m3p12, h4c = u * h3c + (hb * m2p12 - hc * p11),
                       h4d = u * h3d + hc * m3p12, h4e = v * h3d + hc * m3p22;
+#endif
             S4a += h4a * fnn; S4b += h4b * fnn; S4c += h4c * fnn; S4d += h4d * fnn; S4e += h4e * fnn;
         };
         auto run = [&](int c0, int len, auto GW, f2v (&U)[6]) {
@@ -1984,7 +2001,11 @@ __device__ __forceinline__ f2v galaxy_sums_px2(const f2v *tp, int n_dev, int nc,
         auto comp = [&](auto HI, const f2v *k, f2v d1, f2v d2, f2v hd1, f2v hd2) {
             constexpr bool hi = decltype(HI)::value;
 #define PXB(i) (hi ? k[i].yy : k[i].xx)
+#if CELESTE_MUTANT == 5
+            const f2v p11 = PXB(0), p12 = PXB(1), p22 = PXB(2), w0 = PXB(3), wd = PXB(4), nu = k[5].xx;
+#else
             const f2v p11 = PXB(0), p12 = PXB(1), p22 = PXB(2), w0 = PXB(3), wd = PXB(4), nu = PXB(5);
+#endif
 #undef PXB
             const f2v u = p11 * d1 + p12 * d2, v = p12 * d1 + p22 * d2;
             const f2v q2 = hd1 * u + hd2 * v;

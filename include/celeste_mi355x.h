@@ -80,7 +80,9 @@ enum {
      * component loop (packed, two components per instruction), the star spline, the per-pixel term and the record
      * entries are fp32, and so are the star / galaxy densities of the neighbours' pre-rendered light (their moments E,
      * var are formed in fp64); the chunk records everything is summed into, the lift and the KL stay fp64.  Measured against the
-     * fp64 path on all 30 000 sources of config 5: 6e-6 / 5e-7 / 1.2e-6 on v / d / h.  No reference counterpart. */
+     * fp64 path on all 30 000 sources of config 5: 6e-6 / 5e-7 / 1.2e-6 on v / d / h.  Entry-wise, on the scale of the fp64
+     * Hessian: |dh_ij| <= 0.1 max(|h_ij|, 0.01 sqrt|h_ii h_jj|), |dd_i| <= 2e-3 max(|d_i|, 0.01 sqrt|h_ii|), |dv| <= 5e-5 |v|
+     * (worst measured 2.1e-2 / 4.9e-4 / 1.0e-5).  No reference counterpart. */
     CELESTE_FLAG_FP32 = 8u,
     /* split variant of the pixel sum (measurement aid): the pixel kernel writes one
      * 68-double record per visited pixel to HBM and a separate streaming kernel forms the per-patch sums

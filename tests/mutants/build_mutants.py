@@ -9,7 +9,9 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
 CSRC = os.path.join(ROOT, "celeste.jl_amd", "csrc")
-MUTANTS = {1: "iota_by_column", 2: "sky_transposed", 3: "one_stamp_for_all"}
+MUTANTS = {1: "iota_by_column", 2: "sky_transposed", 3: "one_stamp_for_all",
+           # single-precision code only (CELESTE_FLAG_FP32)
+           4: "px2_h4c_dropped_term", 5: "px2_grad_nu_low_half", 6: "value_f2_p12_low_half", 7: "pk_h4b_m3p11"}
 
 
 def path(k):

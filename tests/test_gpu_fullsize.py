@@ -7,7 +7,7 @@ configs[4] scaled to one GPU's share: overlapping fields, fp32 component loop at
 import numpy as np
 import pytest
 
-from parity_util import assert_parity
+from parity_util import assert_fp32_parity, assert_parity
 
 pytestmark = pytest.mark.gpu
 ALL = 7
@@ -148,11 +148,13 @@ def test_config5_overlapping_fields_fp32(oracle):
     eh = max(np.abs(h32[t] - h64[t]).max() / np.abs(h64[t]).max() for t in tg)
     print("fp32 vs fp64 device:", ev, ed, eh)
     assert ev <= 1e-4 and ed <= 1e-4 and eh <= 1e-4
+    print("fp32 vs fp64 device, entry-wise:", assert_fp32_parity((v32, d32, h32), (v64, d64, h64), h64, "config5 fp32 vs fp64 device"))
     sample = sorted(set(list(range(0, S, 60)) + list(np.argsort(-seen)[:6])))
     ov, od, oh, ocnt, ost = oracle.elbo_batch(ctx.problem, f.vp, sample, ALL)
     assert np.array_equal(cnt32[sample], ocnt)
     assert np.max(np.abs(v32[sample] - ov) / np.abs(ov)) <= 1e-4
     assert max(np.abs(d32[t] - od[k]).max() / np.abs(od[k]).max() for k, t in enumerate(sample)) <= 1e-4
+    assert_fp32_parity((v32[sample], d32[sample], h32[sample]), (ov, od, oh), oh, "config5 fp32 vs oracle")
     errs = assert_parity((v64[sample], d64[sample], h64[sample], cnt64[sample], st64[sample]), (ov, od, oh, ocnt, ost), "config5 fp64")
     print("config5 fp64 sample of %d" % len(sample), errs)
     costs = [estimate_time(row) for row in f.patches]
@@ -164,6 +166,7 @@ def test_config5_overlapping_fields_fp32(oracle):
             vg, dg, _, _, _ = ctx.eval_batch(f.vp, shard, 1 | 4 | cabi.FLAG_FP32)
             assert np.max(np.abs(vg - v32[shard]) / np.abs(v32[shard])) <= 1e-6
             assert np.max(np.abs(dg - d32[shard]).max(axis=1) / np.abs(d32[shard]).max(axis=1)) <= 1e-5
+            assert_fp32_parity((vg, dg, None), (v64[shard], d64[shard], None), h64[shard], "config5 fp32 gradient-only")
 
 
 def test_config5_full_size(oracle):

@@ -4,7 +4,7 @@ import os
 import numpy as np
 import pytest
 
-from parity_util import assert_parity, rel_err
+from parity_util import assert_fp32_parity, assert_parity, fp32_errors, rel_err
 
 # CELESTE_FUZZ_SEEDS=N: every seeded fuzz test with N seeds instead of its default handful (a long run on a GPU box)
 FUZZ_SEEDS = int(os.environ.get("CELESTE_FUZZ_SEEDS", "0"))
@@ -101,6 +101,7 @@ def test_fp32_component_loop_within_1e4(oracle):
     f = synthetic.make_field(200, 240, 40, seed=4, nan_fraction=0.002)
     ctx = _ctx(f)
     tg = list(range(40))
+    ref_h = oracle.elbo_batch(ctx.problem, f.vp, tg, ALL)[2]     # the entry-wise scales, gradient-only mode included
     for flags in (1 | 4 | cabi.FLAG_FP32, ALL | cabi.FLAG_FP32):
         v, d, h, cnt, st = ctx.eval_batch(f.vp, tg, flags)
         ov, od, oh, ocnt, ost = oracle.elbo_batch(ctx.problem, f.vp, tg, flags & 7)
@@ -112,6 +113,23 @@ def test_fp32_component_loop_within_1e4(oracle):
             eh = max(np.abs(h[t] - oh[t]).max() / np.abs(oh[t]).max() for t in tg)
             assert eh <= 1e-4, eh
             print("fp32 errs", ev, ed, eh)
+        print("fp32 entry-wise", flags, assert_fp32_parity((v, d, h), (ov, od, oh), ref_h, "fp32 field, flags %d" % flags))
+
+
+def test_fp32_split_packed_and_256_pixel_chunks_against_the_oracle(oracle):
+    """the single-precision combinations the fused mode does not run: CELESTE_FLAG_FP32 | CELESTE_FLAG_SPLIT
+    (pixel_kernel<3, float>, galaxy_sums_pk), | CELESTE_FLAG_PACKED_HESS and CELESTE_FP32_CHUNK_256 -- against the fp64
+    oracle entry by entry, and against the fused fp32 result; all targets and a subset (partial tiles, NaN pixels,
+    neighbours)"""
+    from celeste_jl_amd import synthetic, cabi
+    f = synthetic.make_field(160, 200, 40, seed=11, nan_fraction=0.005)
+    ctx = _ctx(f)
+    for tg in (list(range(len(f.catalog))), [7, 3, 21]):
+        ref = oracle.elbo_batch(ctx.problem, f.vp, tg, ALL)
+        fused = ctx.eval_batch(f.vp, tg, ALL | cabi.FLAG_FP32)
+        assert np.array_equal(fused[3], ref[3]) and (fused[4] == 0).all()
+        w = assert_fp32_parity(fused, ref, ref[2], "fp32 field seed 11")
+        print("fp32 fused", w, "variants", _check_fp32_variants(ctx, f.vp, tg, fused, ref, "fp32 field seed 11"))
 
 
 def _affine_variable_psf_field(seed=7):
@@ -198,6 +216,7 @@ def test_multifield_overlapping_images(oracle):
     v, d, h, cnt, st = ctx.eval_batch(f.vp, tg, 1 | 4 | cabi.FLAG_FP32)
     assert np.max(np.abs(v - ref[0]) / np.abs(ref[0])) <= 1e-4
     assert max(np.abs(d[t] - ref[1][t]).max() / np.abs(ref[1][t]).max() for t in tg) <= 1e-4
+    assert_fp32_parity((v, d, None), ref, ref[2], "multifield, fp32 gradient-only")
 
 
 def test_sparse_patch_list_abi(oracle):
@@ -572,6 +591,8 @@ def _randomised_field(oracle, seed, seed0, size_range, s_range):
         assert np.max(np.abs(g32[0] - r32[0]) / np.abs(r32[0])) <= 1e-4
         if flags & 3:
             assert max(np.abs(g32[1][k] - r32[1][k]).max() / np.abs(r32[1][k]).max() for k in range(len(tg))) <= 1e-4
+        ref_h = r32[2] if flags & 2 else oracle.elbo_batch(ctx.problem, f.vp, tg, flags | 2)[2] if flags & 1 else None
+        assert_fp32_parity(g32, r32, ref_h, "fuzz %d fp32, flags %d" % (seed, flags))
     g = ctx.eval_batch(f.vp, tg, flags, raise_on_error=False)
     if g[4].any():
         _report_unexpected_statuses(cel, f, ctx, psf_K, tg, flags, g, "fuzz %d (seed0 %d)" % (seed, seed0))
@@ -592,14 +613,11 @@ def _randomised_field(oracle, seed, seed0, size_range, s_range):
     del _FUZZ_HISTORY[:-4]
 
 
-@pytest.mark.parametrize("seed", range(FUZZ_SEEDS or 10))
-def test_single_precision_mode_counts_and_masks_like_the_fp64_path(seed):
-    """CELESTE_FLAG_FP32 runs its own pixel loop (two pixels per lane, pixel_iter_px2): on fields with NaN pixels, punched
-    bitmaps, a missing patch, one-column patches, tiny patches (chunks with fewer than 64 / 128 pixels) and psf_K 1 / 3 the
-    pixel COUNTERS and statuses must equal the fp64 path's exactly, values / gradients / Hessians agree at the mode's 1e-4,
-    and gradient-only equals the gradient of the Hessian mode"""
+def _fp32_fuzz_scene(seed):
+    """the fields of test_single_precision_mode_counts_and_masks_like_the_fp64_path (also measured by
+    tools/gpu_fp32_entry_errors.py): context, field, targets, (H, W, S, psf_K)"""
     import celeste_jl_amd as cel
-    from celeste_jl_amd import synthetic, cabi
+    from celeste_jl_amd import synthetic
     rng = np.random.default_rng(7000 + seed)
     H, W = int(rng.integers(50, 150)), int(rng.integers(50, 150))
     S = int(rng.integers(2, 12))
@@ -643,6 +661,79 @@ def test_single_precision_mode_counts_and_masks_like_the_fp64_path(seed):
     from celeste_jl_amd.model import neighbor_map
     ctx = cel.FieldContext(f.images, f.patches, neighbor_map(f.patches), psf_K=psf_K)
     tg = rng.permutation(S).tolist()
+    return ctx, f, tg, (H, W, S, psf_K)
+
+
+# The single-precision launches that share pixel_iter's per-pixel float records with the fused mode but sum them differently.
+# Bounds measured on the MI355X (tools/gpu_fp32_entry_errors.py, profiles/fp32_entry_errors_mi355x.json), 4x headroom or more,
+# as the worst fp32_errors ratio (parity_util: the entry-wise scales of the fp64 Hessian) between the two results:
+# - CELESTE_FLAG_SPLIT against the fused fp32 mode: the same float entries per pixel, summed in fp64 per 64-pixel tile
+#   (record_sum_kernel) instead of folded in pairs of pixels in float first;
+# - CELESTE_FP32_CHUNK_256 against the 512-pixel chunks: identical per-pixel float sums, only the fp64 chunk records are
+#   grouped differently.
+# (measured worst: 1.10e-4 and 8.8e-14)
+FP32_SPLIT_VS_FUSED = 5e-4
+FP32_CHUNK256_VS_512 = 4e-13
+
+
+def _fp32_worst(a, b, ref_h):
+    e = fp32_errors(a, b, ref_h)
+    return max(float(x.max()) for x in e.values() if x is not None and x.size)
+
+
+def _fp32_variants(ctx, vp, tg):
+    """the fp32 Hessian mode's other launches: split, packed Hessian, 256-pixel chunks (the environment variable is read at
+    every call)"""
+    from celeste_jl_amd import cabi
+    out = {"split": ctx.eval_batch(vp, tg, ALL | cabi.FLAG_FP32 | cabi.FLAG_SPLIT),
+           "packed": ctx.eval_batch(vp, tg, ALL | cabi.FLAG_FP32 | cabi.FLAG_PACKED_HESS)}
+    old = os.environ.get("CELESTE_FP32_CHUNK_256")
+    os.environ["CELESTE_FP32_CHUNK_256"] = "1"
+    try:
+        out["chunk256"] = ctx.eval_batch(vp, tg, ALL | cabi.FLAG_FP32)
+    finally:
+        if old is None:
+            del os.environ["CELESTE_FP32_CHUNK_256"]
+        else:
+            os.environ["CELESTE_FP32_CHUNK_256"] = old
+    return out
+
+
+def _check_fp32_variants(ctx, vp, tg, fused, ref, what, ref_h=None):
+    """split / packed / 256-pixel-chunk fp32 launches against the fused fp32 result `fused` and the fp64 reference `ref`
+    (oracle or fp64 device; ref_h: its Hessians, default ref[2])"""
+    ref_h = ref[2] if ref_h is None else ref_h
+    var = _fp32_variants(ctx, vp, tg)
+    v32, d32, h32, c32, s32 = fused
+    # split: exact counters and statuses, the entry-wise criterion against the fp64 reference, and close to the fused sums
+    vs, ds, hs, cs, ss = var["split"]
+    assert np.array_equal(cs, c32) and np.array_equal(ss, s32), (what, "split counters / statuses")
+    assert all(np.array_equal(hs[k], hs[k].T) for k in range(len(tg)))
+    assert_fp32_parity((vs, ds, hs), ref, ref_h, what + ", split")
+    e_split = _fp32_worst((vs, ds, hs), (v32, d32, h32), ref_h)
+    assert e_split <= FP32_SPLIT_VS_FUSED, (what, "split against fused fp32", e_split)
+    # packed Hessian: the upper triangle of the unpacked fp32 Hessian, column by column, bit for bit
+    from celeste_jl_amd import cabi
+    vp_, dp, hp, cp, sp = var["packed"]
+    J = np.concatenate([np.full(j + 1, j) for j in range(44)]); I = np.concatenate([np.arange(j + 1) for j in range(44)])
+    assert hp.shape == (len(tg), cabi.HP)
+    assert np.array_equal(hp, h32[:, I, J]) and np.array_equal(vp_, v32) and np.array_equal(dp, d32) and np.array_equal(cp, c32)
+    # 256-pixel chunks: the same counters; v, d, h regrouped fp64 sums of the same float entries
+    vc, dc, hc, cc, sc = var["chunk256"]
+    assert np.array_equal(cc, c32) and np.array_equal(sc, s32), (what, "256-pixel chunks counters / statuses")
+    e_chunk = _fp32_worst((vc, dc, hc), (v32, d32, h32), ref_h)
+    assert e_chunk <= FP32_CHUNK256_VS_512, (what, "256- against 512-pixel chunks", e_chunk)
+    return {"split_vs_fused": e_split, "chunk256_vs_512": e_chunk}
+
+
+@pytest.mark.parametrize("seed", range(FUZZ_SEEDS or 10))
+def test_single_precision_mode_counts_and_masks_like_the_fp64_path(seed):
+    """CELESTE_FLAG_FP32 runs its own pixel loop (two pixels per lane, pixel_iter_px2): on fields with NaN pixels, punched
+    bitmaps, a missing patch, one-column patches, tiny patches (chunks with fewer than 64 / 128 pixels) and psf_K 1 / 3 the
+    pixel COUNTERS and statuses must equal the fp64 path's exactly, values / gradients / Hessians agree at the mode's 1e-4,
+    and gradient-only equals the gradient of the Hessian mode"""
+    from celeste_jl_amd import cabi
+    ctx, f, tg, (H, W, S, psf_K) = _fp32_fuzz_scene(seed)
     v64, d64, h64, c64, s64 = ctx.eval_batch(f.vp, tg, ALL)
     v32, d32, h32, c32, s32 = ctx.eval_batch(f.vp, tg, ALL | cabi.FLAG_FP32)
     assert np.array_equal(c64, c32) and np.array_equal(s64, s32) and (s64 == 0).all()
@@ -651,11 +742,14 @@ def test_single_precision_mode_counts_and_masks_like_the_fp64_path(seed):
     ed = max(np.abs(d32[k] - d64[k]).max() / np.abs(d64[k]).max() for k in range(len(tg)))
     eh = max(np.abs(h32[k] - h64[k]).max() / np.abs(h64[k]).max() for k in range(len(tg)))
     assert max(ev, ed, eh) <= 1e-4, (ev, ed, eh)
+    worst = assert_fp32_parity((v32, d32, h32), (v64, d64, h64), h64, "fp32 fuzz %d" % seed)
     assert all(np.array_equal(h32[k], h32[k].T) for k in range(len(tg)))
     vg, dg, _, cg, _ = ctx.eval_batch(f.vp, tg, 1 | 4 | cabi.FLAG_FP32)
     assert np.array_equal(cg, c64)
     assert float(np.max(np.abs(vg - v64) / np.abs(v64))) <= 1e-4
     assert max(np.abs(dg[k] - d64[k]).max() / np.abs(d64[k]).max() for k in range(len(tg))) <= 1e-4
+    assert_fp32_parity((vg, dg, None), (v64, d64, None), h64, "fp32 fuzz %d, gradient-only" % seed)
+    _check_fp32_variants(ctx, f.vp, tg, (v32, d32, h32, c32, s32), (v64, d64, h64), "fp32 fuzz %d" % seed)
     # a target's fp32 result does not depend on the size of the batch it is in: beyond 768 targets the neighbours' light is
     # rendered by one wavefront per item instead of two (celeste_abi.hip VALUE_WIDE_MAX) -- same per-pixel arithmetic
     # (value_pixels_f2), so the SAME targets repeated into a batch of > 768 give the same bits, masks and counters included
@@ -668,7 +762,7 @@ def test_single_precision_mode_counts_and_masks_like_the_fp64_path(seed):
         sl = slice(r * n, (r + 1) * n)
         assert np.array_equal(vb[sl], v32) and np.array_equal(db[sl], d32) and np.array_equal(hb[sl], h32)
         assert np.array_equal(cb[sl], c32) and np.array_equal(sb[sl], s32)
-    print("fp32 fuzz", seed, (H, W, S), "psf_K", psf_K, "errors", ev, ed, eh)
+    print("fp32 fuzz", seed, (H, W, S), "psf_K", psf_K, "errors", ev, ed, eh, "entry-wise", worst)
 
 
 @pytest.mark.parametrize("seed", range(FUZZ_SEEDS or 6))

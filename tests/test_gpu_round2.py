@@ -324,7 +324,7 @@ def test_variable_sky_calibration_and_psf_map_on_the_device(oracle):
     multi-active paths against the oracle (SDSSIO.jl:56-99, 239-299; elbo_objective.jl:374-385)"""
     import celeste_jl_amd as cel
     from celeste_jl_amd import synthetic, cabi
-    from parity_util import assert_parity, rel_err
+    from parity_util import assert_fp32_parity, assert_parity, rel_err
     f = synthetic.make_field(300, 340, 60, seed=41, variable=True, nan_fraction=0.005)
     ctx = cel.FieldContext(f.images, f.patches, f.neighbors)
     assert ctx.problem.c.n_stamps > 200
@@ -337,6 +337,7 @@ def test_variable_sky_calibration_and_psf_map_on_the_device(oracle):
     # (the fp32 mode's stated tolerance is norm-scaled: SURVEY.md 8(d) config 5, "1e-4 relative on v and on |d|_inf-scaled d")
     assert max(np.abs(d32[t] - ref[1][t]).max() / np.abs(ref[1][t]).max() for t in tg) <= 1e-4
     assert max(np.abs(h32[t] - ref[2][t]).max() / np.abs(ref[2][t]).max() for t in tg) <= 1e-4
+    assert_fp32_parity((v32, d32, h32), ref, ref[2], "variable field, fp32")
     g = ctx.eval_batch(f.vp, tg, 1 | 4)
     assert np.max(np.abs(g[0] - ref[0]) / np.abs(ref[0])) <= 1e-8 and max(rel_err(g[1][t], ref[1][t]) for t in tg) <= 1e-8
     # two overlapping active sources (Sa = 2) on the same planes
