@@ -6,8 +6,8 @@ One "step" = one sweep of elbo() over every source of the workload, inputs resid
   --config 3 (default)  BASELINE.json configs[2] / configs[3]: ONE synthetic 2048x1489x5 SDSS-size field, ~2000
                         star+galaxy sources, fp64.
   --config 5            BASELINE.json configs[4]: 16 overlapping SDSS-size fields (80 images, ~30k sources, sparse
-                        patch list), fp32 component loop (--dtype f32, the default for this config), checked inside the
-                        run against the fp64 device path at 1e-4.
+                        patch list), fp32 component loop (--dtype f32, the default for this config); with --full also
+                        checked inside the run against the fp64 device path at 1e-4.
 
 With --gpus N the SAME workload is sharded by source across the N ranks ("strong" scaling, the default: this is
 BASELINE configs[3], the reference's one-field source list drained by N workers, ParallelRun.jl:546-607): every rank
@@ -19,6 +19,15 @@ before the clock stops.  --scaling weak gives every rank its own field instead (
 A plain `python bench.py --gpus N` (no launcher, no RANK in the environment) starts its N ranks itself under
 torch.distributed.run; however it was started, the run refuses to go on unless WORLD_SIZE == --gpus, RCCL has a device per
 rank, and an all_reduce over the gather's backend counts N ranks (`ranks_seen` in the line).
+
+A plain run does what its headline needs and nothing more: it renders the field, warms up, times the K steps, writes
+--dump-outputs / --check-dir if asked, and prints the line.  --full adds everything else the benchmark measures or checks:
+kernel times and rooflines, the steady-state repeat of a short loop, the secondary figures (gradient-only, host API,
+single calls, optimiser, joint inference, shard projection, split variant), rocprofv3 counter passes, the variable_psf and
+config5 sub-records, the CPU baseline, the fp32-vs-fp64 check of --config 5, and at N > 1 the sweep without the gather
+and the group driver.  The --no-* options leave parts of --full out.
+
+Every run renders its field itself: no run reads a field an earlier run left behind.
 
 Prints ONE JSON line on rank 0 (contract in the task description).
 """
@@ -57,12 +66,12 @@ def profile_facts():
         return None
 
 
-def live_pmc(args, timeout_s=60, split=False):
+def live_pmc(args, timeout_s=120, split=False):
     """HBM traffic and VALU issue utilisation of pixel_kernel<2, double> (split=True: HBM traffic of record_sum_kernel,
     the split variant's streaming sum) measured in THIS run: rocprofv3 --pmc passes (FETCH_SIZE, WRITE_SIZE, SQ
     counters -- separate passes with --kernel-trace only, as the guide's HBM section prescribes) over a few sweeps of
-    the same field in a child process.  None when rocprofv3 is absent, fails or times out; the line then falls back
-    to the committed figures of profiles/hbm_traffic.json and says so."""
+    the same field in a child process, which renders the field itself.  None when rocprofv3 is absent, fails or times
+    out; the line then falls back to the committed figures of profiles/hbm_traffic.json and says so."""
     import csv, glob, shutil, subprocess, tempfile
     exe = shutil.which("rocprofv3") or "/opt/rocm/bin/rocprofv3"
     if not os.path.exists(exe):
@@ -147,6 +156,8 @@ def generator_digest():
 
 
 def build_field(H, W, n_sources, seed, cache=True, variable=False):
+    """The synthetic field of the config-3 workload.  cache: keep it pickled under /tmp for the tests and tools that load the
+    same field many times; the benchmark's own runs pass cache=False."""
     from celeste_jl_amd import synthetic
     return _cached("/tmp/celeste_field_%d_%d_%d_%d%s_%s.pkl" % (H, W, n_sources, seed, "_var" if variable else "", generator_digest()),
                    lambda: synthetic.make_field(H, W, n_sources, seed=seed, variable=variable,
@@ -297,26 +308,32 @@ def main():
     ap.add_argument("--sources", type=int, default=None)
     ap.add_argument("--grid", default="4,4", help="config 5: grid of overlapping fields")
     ap.add_argument("--seed", type=int, default=None)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="only the timed sweep and the roofline")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beyond the headline (module docstring); without it the run times "
+                         "the steps and prints the line")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: no CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="--full: only the timed sweep and the roofline")
     ap.add_argument("--no-live-pmc", action="store_true",
-                    help="do not run the rocprofv3 counter passes; report the committed profiles/hbm_traffic.json figures")
+                    help="--full: do not run the rocprofv3 counter passes; report the committed profiles/hbm_traffic.json figures")
     ap.add_argument("--pmc-child", default=None, choices=("fused", "split", "optim"), help=argparse.SUPPRESS)   # the profiled child of live_pmc / tools/profile_round.sh
     ap.add_argument("--no-config5", action="store_true",
-                    help="config 3, one GPU: do not append the config5 sub-record (a short full-size --config 5 --dtype f32 run)")
+                    help="--full, config 3, one GPU: do not append the config5 sub-record (a short full-size --config 5 --dtype f32 "
+                         "run)")
     ap.add_argument("--kernels-in-pass", action="store_true",
-                    help="record the kernels' HIP-event durations inside the timed steps themselves (one synchronisation per "
-                         "step) instead of in a pass of their own: kernels_ms then sums to at most ms_per_step by construction")
+                    help="--full: record the kernels' HIP-event durations inside the timed steps themselves (one synchronisation "
+                         "per step) instead of in a pass of their own: kernels_ms then sums to at most ms_per_step by construction")
     ap.add_argument("--shard-projection", action="store_true",
-                    help="one GPU: sweep rank 0's cost-balanced shard of this workload for N = 1, 2, 4, 8 ranks (fp32 and fp64) -- "
-                         "a one-GPU bound on the strong-scaling efficiency (used for the config5 sub-record)")
+                    help="--full, one GPU: sweep rank 0's cost-balanced shard of this workload for N = 1, 2, 4, 8 ranks (fp32 and "
+                         "fp64) -- a one-GPU bound on the strong-scaling efficiency (used for the config5 sub-record)")
     ap.add_argument("--variable-psf", action="store_true",
                     help="config 3 with the PSF the reference's production path uses: an SDSSPSFMap evaluated at every source "
                          "(SDSSIO.jl:239-299) -- one 51x51 stamp, hence one set of spline coefficients, per (source, band) -- plus a "
                          "varying sky plane and per-row calibration, instead of AccuracyBenchmark's ConstantPSFMap")
-    ap.add_argument("--no-variable-psf", action="store_true", help="config 3, one GPU: do not append the variable_psf sub-record")
+    ap.add_argument("--no-variable-psf", action="store_true",
+                    help="--full, config 3, one GPU: do not append the variable_psf sub-record")
     ap.add_argument("--no-group-driver", action="store_true",
-                    help="N > 1: do not let rank 0 repeat the sweep through celeste_group_* (the in-library driver) after the ranks' run")
+                    help="--full, N > 1: do not let rank 0 repeat the sweep through celeste_group_* (the in-library driver) after "
+                         "the ranks' run")
     ap.add_argument("--check-dir", default=None,
                     help="every rank writes its gathered (v, d) of the last sweep to <dir>/rank<r>.npz (tests)")
     ap.add_argument("--dump-outputs", default=None, metavar="DIR",
@@ -329,6 +346,8 @@ def main():
         raise SystemExit("--gpus must be >= 1")
     if args.steps is not None and args.steps < 1:
         raise SystemExit("--steps must be >= 1")
+    if (args.kernels_in_pass or args.shard_projection) and not args.full:
+        raise SystemExit("--kernels-in-pass and --shard-projection report figures of --full: add --full")
     if args.driver == "group":
         if int(os.environ.get("RANK", "0")) != 0:
             return               # (started under a launcher: the group lives in ONE process -- rank 0's)
@@ -400,25 +419,16 @@ def main():
     # ---- the workload: the same field(s) on every rank (strong), or one per rank (weak) ----
     seed = args.seed if strong else args.seed + rank
 
-    def make():
-        if args.config == 3:
-            return build_field(args.height, args.width, args.sources, seed, variable=args.variable_psf)
-        grid = tuple(int(x) for x in args.grid.split(","))
-        return build_multifield(grid, args.height, args.width, args.sources, seed)
-    if use_dist and strong and args.config == 3:
-        if rank == 0:      # one rank renders the field and caches it; the others load the cache
-            fld = make()
-        dist.barrier()
-        if rank != 0:
-            fld = make()
+    if args.config == 3:
+        fld = build_field(args.height, args.width, args.sources, seed, cache=False, variable=args.variable_psf)
     else:
-        fld = make()
+        fld = build_multifield(tuple(int(x) for x in args.grid.split(",")), args.height, args.width, args.sources, seed)
     S = len(fld.catalog)
     ctx = cel.FieldContext(fld.images, fld.patches, fld.neighbors, device=dev.index)
     # what celeste_ctx_create costs once the process has its runtime and code object (the first call of a process carries
     # ~0.1 s of one-time HIP initialisation): a second context of the same marshalled problem, created and released (rank 0)
     ctx_create_ms = None
-    if rank == 0 and not args.pmc_child:
+    if args.full and rank == 0 and not args.pmc_child:
         c2 = cel.FieldContext(fld.images, None, fld.neighbors, device=dev.index, problem=ctx.problem)
         ctx_create_ms = c2.create_ms
         c2.close()
@@ -498,24 +508,25 @@ def main():
         dump_outputs(args.dump_outputs, {k: a for k, a in dumped.items() if a is not None})
     pixel_visits_local = int(cnt_loc[:, 0].sum())
 
-    # ---- dominant-kernel duration: HIP events recorded by the library on the launch stream, averaged ----
-    ctx.enable_timing(True)
-    kms = []
+    # ---- --full: dominant-kernel duration: HIP events recorded by the library on the launch stream, averaged ----
     blk0 = sweep.blocks[0].data_ptr()
-    for _ in range(min(20, max(3, args.steps))):
-        if sweep.n > 0:
-            ctx.eval_batch_device(d_vp.data_ptr(), sweep.n, sweep.d_tg.data_ptr(), flags, blk0, blk0 + 8 * sweep.width,
-                                  sweep.d_h.data_ptr() if sweep.d_h is not None else 0, sweep.d_cnt.data_ptr(),
-                                  sweep.d_st.data_ptr(), sweep.compute_stream.cuda_stream)
-        sweep.wait()
-        kms.append(ctx.last_kernel_ms())
-    ctx.enable_timing(False)
-    kms = np.array(kms_in_pass if kms_in_pass else kms).mean(axis=0)
-    sync()
+    if args.full:
+        ctx.enable_timing(True)
+        kms = []
+        for _ in range(min(20, max(3, args.steps))):
+            if sweep.n > 0:
+                ctx.eval_batch_device(d_vp.data_ptr(), sweep.n, sweep.d_tg.data_ptr(), flags, blk0, blk0 + 8 * sweep.width,
+                                      sweep.d_h.data_ptr() if sweep.d_h is not None else 0, sweep.d_cnt.data_ptr(),
+                                      sweep.d_st.data_ptr(), sweep.compute_stream.cuda_stream)
+            sweep.wait()
+            kms.append(ctx.last_kernel_ms())
+        ctx.enable_timing(False)
+        kms = np.array(kms_in_pass if kms_in_pass else kms).mean(axis=0)
+        sync()
     # the same loop once more when the timed one was short: what a step costs once the chip has left its idle power state
     # (a secondary figure: `value` stays the K steps the caller asked for)
     steady = None
-    if args.steps < 100 and args.config == 3 and not args.pmc_child:
+    if args.full and args.steps < 100 and args.config == 3 and not args.pmc_child:
         for _ in range(20):
             sweep.step(d_vp.data_ptr())
         sync()
@@ -531,7 +542,7 @@ def main():
     # (celeste_group_*: worker threads, ncclCommInitAll + ncclAllGather inside the library) -- while the other ranks wait on the
     # host (the rendezvous store, not a collective: their GPUs stay idle for the group's members)
     group_rec = None
-    if use_dist and world > 1 and not args.no_group_driver and not args.pmc_child:
+    if args.full and use_dist and world > 1 and not args.no_group_driver and not args.pmc_child:
         store = dist.distributed_c10d._get_default_store()
         if rank == 0:
             try:
@@ -548,7 +559,7 @@ def main():
     # N > 1: every rank's sweep of its own shard WITHOUT the catalog gather (same launches, wall clock between two
     # device synchronisations) -- what separates load imbalance / small-shard latency from the cost of the exchange
     sweep_only_ms = None
-    if use_dist and world > 1:
+    if args.full and use_dist and world > 1:
         cs = sweep.compute_stream.cuda_stream
 
         def shard_only():
@@ -570,7 +581,7 @@ def main():
         sweep_only_ms = [float(t.item()) for t in allms]
         sync()
 
-    extras = world == 1 and not args.no_extras
+    extras = args.full and world == 1 and not args.no_extras
     d_tg = sweep.d_tg
     d_v = torch.zeros(S, dtype=torch.float64, device=dev)
     d_d = torch.zeros(S, 44, dtype=torch.float64, device=dev)
@@ -595,7 +606,7 @@ def main():
         torch.cuda.synchronize(dev)
         out_extra["grad_only_sources_per_sec_rank0"] = S / ((time.perf_counter() - tg0) / args.steps)
 
-    if args.config == 5 and world == 1 and args.dtype == "f32":
+    if args.full and args.config == 5 and world == 1 and args.dtype == "f32":
         # the configuration's stated tolerance: fp32 component loop within 1e-4 of the fp64 device path, every source
         d_h64 = torch.zeros(S, 44, 44, dtype=torch.float64, device=dev)
         ctx.eval_batch_device(d_vp.data_ptr(), S, d_tg.data_ptr(), FLAGS_ALL, d_v.data_ptr(), d_d.data_ptr(),
@@ -633,7 +644,8 @@ def main():
     # HBM bytes and VALU utilisation of the dominant kernel: measured now when rocprofv3 can run here, else the
     # committed figures (the flop count per pixel visit always comes from the ISA of the tree, tools/count_flops.py)
     pmc_live = pmc_split = None
-    if world == 1 and rank == 0 and args.config == 3 and args.dtype == "f64" and (extras or args.variable_psf) and not args.no_live_pmc:
+    if args.full and world == 1 and rank == 0 and args.config == 3 and args.dtype == "f64" and (extras or args.variable_psf) \
+            and not args.no_live_pmc:
         pmc_live = live_pmc(args)
         if pmc_live:
             facts = dict(facts, **pmc_live)
@@ -680,14 +692,6 @@ def main():
         n_total = int(sum(p[0] for p in per_rank))           # sources evaluated per step by the whole job
         ms_per_step = dt / args.steps * 1e3
         value = n_total / (dt / args.steps)
-        # the star spline coefficients (53 x 53 f64 = 22 472 B per stamp) count once per band per sweep when
-        # the PSF map is constant, per patch otherwise: the context's distinct stamps are exactly that
-        spline_bytes = int(ctx.problem.c.n_stamps) * 53 * 53 * 8
-        alg_bytes = stats["algorithmic_bytes"] + spline_bytes   # of rank 0's launch
-        achieved = alg_bytes / (kms[1] * 1e-3) / 1e9
-        fpp = facts.get("flops_per_pixel_visit_f32" if args.dtype == "f32" else "flops_per_pixel_visit")
-        peak_fl = FP32_VECTOR_PEAK_TFLOPS if args.dtype == "f32" else FP64_VECTOR_PEAK_TFLOPS
-        kname = "pixel_kernel<2, %s>" % ("float" if args.dtype == "f32" else "double")
         if args.config == 3:
             workload = ("BASELINE.json configs[%d]: synthetic %dx%dx5 SDSS-size field, %d star+galaxy sources%s, fp64, "
                         "Sa=1 with value-only neighbours, psf_K=2%s"
@@ -716,68 +720,82 @@ def main():
                        "neighbor_links_rank0": stats["neighbor_links"],
                        "parallelism": ("one field, targets sharded by estimated cost, images replicated, one all-gather of "
                                        "(v, d) per sweep" if strong else "one field per GPU, all-gather of (v, d) per sweep")},
-            "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": achieved / HBM_PEAK_GBS,
-                         "traffic": facts.get("pixel_kernel_bytes_per_launch") if (world == 1 and args.config == 3 and
-                                                                                     args.dtype == "f64") else None,
-                         "traffic_source": facts.get("source"), "traffic_measured_in_this_run": bool(pmc_live),
-                         "kernel": kname, "kernel_ms": float(kms[1]),
-                         "algorithmic_bytes_per_launch": alg_bytes, "spline_coefficient_bytes": spline_bytes,
-                         "psf_stamps": int(ctx.problem.c.n_stamps),
-                         "valu_utilization": facts.get("pixel_kernel_valu_utilization") if args.dtype == "f64" else None},
             "timing_method": ("value / ms_per_step: wall clock around K sweeps (launch chain + catalog gather) between two device "
-                              "synchronisations + barriers, max over ranks; kernels_ms / roofline.kernel_ms: HIP events recorded by "
-                              "the library on the launch stream, " + ("inside the timed steps (one synchronisation per step)"
-                                                                     if args.kernels_in_pass else "in a pass of their own after the timed region")),
+                              "synchronisations + barriers, max over ranks"),
             "parity_pin": parity_pin_status(),
-            # celeste_ctx_create (the C call, second context of the process): image planes up, every PSF stamp conditioned +
-            # spline-prefiltered on the device (the ImagePatch constructor, imaged_sources.jl:97-107), patch / neighbour / work tables
-            "context_create_ms": ctx_create_ms,
-            "kernels_ms": {"prep": float(kms[0]), "pixel": float(kms[1]), "lift": float(kms[2])},
-            # where ms_per_step goes (rank 0): the steps of the timed loop one by one, the part of a step no kernel accounts
-            # for, and the shader clock the chip reported right behind the loop -- a short run (--steps 20 after --warmup 5 is
-            # 18 ms of work) measures a chip that is still leaving its idle power state; step_ms shows it
+            # where ms_per_step goes (rank 0): the steps of the timed loop one by one and the shader clock the chip reported right
+            # behind the loop -- a short run (--steps 20 after --warmup 5 is 18 ms of work) measures a chip that is still leaving
+            # its idle power state; step_ms shows it
             "step_ms": {"min": float(step_ms.min()), "p50": float(np.median(step_ms)), "max": float(step_ms.max()),
                         "first": float(step_ms[0]), "last": float(step_ms[-1]),
                         "first_quarter_mean": float(step_ms[:max(1, len(step_ms) // 4)].mean()),
                         "last_quarter_mean": float(step_ms[-max(1, len(step_ms) // 4):].mean()),
                         "sum": float(step_ms.sum()), "wall_ms": dt * 1e3,
                         "source": "HIP events at the step boundaries of the timed loop, on the launch stream"},
-            "gaps_ms": float(ms_per_step - (kms[0] + kms[1] + kms[2])),
             "sclk_mhz_after_loop": sclk_after,
-            "pixel_visits_per_sec_rank0": pixel_visits_local / (kms[1] * 1e-3),
         }
-        if fpp:
-            # executed flops: the compiled ISA's count per visit x the (pixel, active source) pairs the kernel counted --
-            # not the patches' areas, which include the last-column pixels that skip the component loop
-            fl = fpp * pixel_visits_local / (kms[1] * 1e-3) / 1e12
-            sus = FP32_SUSTAINED_FMA_TFLOPS if args.dtype == "f32" else FP64_SUSTAINED_FMA_TFLOPS
-            hbm = out["roofline"]
-            # the binding roofline on top: the fused kernel is vector-ALU bound, so `frac` is
-            # the executed-flop fraction of the nominal vector peak; the HBM figures the metric's text asks for sit in `hbm`
-            out["roofline"] = {"bound": "fp32_valu" if args.dtype == "f32" else "fp64_valu",
-                               "achieved": fl, "peak": peak_fl, "unit": "TFLOP/s", "frac": fl / peak_fl,
-                               "traffic": hbm["traffic"], "kernel": kname, "kernel_ms": float(kms[1]),
-                               "sustained_fma_peak": sus, "frac_of_sustained": fl / sus,
-                               "sustained_source": "profiles/r04_fp64_issue_rates.txt: independent FMAs issue every 4.9 cycles per "
-                                                   "SIMD at the clock the chip holds under them, 0.70 (fp64) / 0.80 (packed fp32) of "
-                                                   "the nominal peak (self-measured: `frac` against the nominal peak is the figure "
-                                                   "of record)",
-                               "flops_per_pixel_visit": fpp, "pixel_visits": pixel_visits_local, "dtype": args.dtype,
-                               "flops_source": "tools/count_flops.py on the compiled ISA (profiles/hbm_traffic.json; "
-                                               "tests/test_dpp_hazard.py holds the file to the tree); every basic block LLVM's loop "
-                                               "annotations place in the pixel loop, guarded blocks (star spline, own-geometry region) "
-                                               "included once per visit: a static count, an upper bound of the executed one by the "
-                                               "rare trips that skip them",
-                               "instruction_mix": facts.get("instruction_mix_f32" if args.dtype == "f32" else "instruction_mix"),
-                               "valu_utilization": hbm["valu_utilization"],
-                               "hbm": hbm,
-                               "note": "valu_utilization = SQ_ACTIVE_INST_VALU x 4 / SIMD-cycles (hbm.traffic_source says where the "
-                                       "counters come from); the HBM-bound kernel of the path is split_variant.kernel; figures are "
-                                       "rank 0's launch"}
-            out["roofline"]["valu"] = {k: out["roofline"][k] for k in ("achieved", "peak", "unit", "frac", "sustained_fma_peak",
-                                                                       "frac_of_sustained", "flops_per_pixel_visit", "pixel_visits",
-                                                                       "dtype", "instruction_mix")}   # (the rounds-1..4 location)
+        if args.full:
+            # the star spline coefficients (53 x 53 f64 = 22 472 B per stamp) count once per band per sweep when
+            # the PSF map is constant, per patch otherwise: the context's distinct stamps are exactly that
+            spline_bytes = int(ctx.problem.c.n_stamps) * 53 * 53 * 8
+            alg_bytes = stats["algorithmic_bytes"] + spline_bytes   # of rank 0's launch
+            achieved = alg_bytes / (kms[1] * 1e-3) / 1e9
+            fpp = facts.get("flops_per_pixel_visit_f32" if args.dtype == "f32" else "flops_per_pixel_visit")
+            peak_fl = FP32_VECTOR_PEAK_TFLOPS if args.dtype == "f32" else FP64_VECTOR_PEAK_TFLOPS
+            kname = "pixel_kernel<2, %s>" % ("float" if args.dtype == "f32" else "double")
+            out["timing_method"] += ("; kernels_ms / roofline.kernel_ms: HIP events recorded by the library on the launch stream, "
+                                     + ("inside the timed steps (one synchronisation per step)" if args.kernels_in_pass
+                                        else "in a pass of their own after the timed region"))
+            out.update({
+                "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                             "frac": achieved / HBM_PEAK_GBS,
+                             "traffic": facts.get("pixel_kernel_bytes_per_launch") if (world == 1 and args.config == 3 and
+                                                                                         args.dtype == "f64") else None,
+                             "traffic_source": facts.get("source"), "traffic_measured_in_this_run": bool(pmc_live),
+                             "kernel": kname, "kernel_ms": float(kms[1]),
+                             "algorithmic_bytes_per_launch": alg_bytes, "spline_coefficient_bytes": spline_bytes,
+                             "psf_stamps": int(ctx.problem.c.n_stamps),
+                             "valu_utilization": facts.get("pixel_kernel_valu_utilization") if args.dtype == "f64" else None},
+                # celeste_ctx_create (the C call, second context of the process): image planes up, every PSF stamp conditioned
+                # + spline-prefiltered on the device (the ImagePatch constructor, imaged_sources.jl:97-107), patch / neighbour /
+                # work tables
+                "context_create_ms": ctx_create_ms,
+                "kernels_ms": {"prep": float(kms[0]), "pixel": float(kms[1]), "lift": float(kms[2])},
+                # the part of a step (rank 0) no kernel accounts for
+                "gaps_ms": float(ms_per_step - (kms[0] + kms[1] + kms[2])),
+                "pixel_visits_per_sec_rank0": pixel_visits_local / (kms[1] * 1e-3),
+            })
+            if fpp:
+                # executed flops: the compiled ISA's count per visit x the (pixel, active source) pairs the kernel counted --
+                # not the patches' areas, which include the last-column pixels that skip the component loop
+                fl = fpp * pixel_visits_local / (kms[1] * 1e-3) / 1e12
+                sus = FP32_SUSTAINED_FMA_TFLOPS if args.dtype == "f32" else FP64_SUSTAINED_FMA_TFLOPS
+                hbm = out["roofline"]
+                # the binding roofline on top: the fused kernel is vector-ALU bound, so `frac` is
+                # the executed-flop fraction of the nominal vector peak; the HBM figures the metric's text asks for sit in `hbm`
+                out["roofline"] = {"bound": "fp32_valu" if args.dtype == "f32" else "fp64_valu",
+                                   "achieved": fl, "peak": peak_fl, "unit": "TFLOP/s", "frac": fl / peak_fl,
+                                   "traffic": hbm["traffic"], "kernel": kname, "kernel_ms": float(kms[1]),
+                                   "sustained_fma_peak": sus, "frac_of_sustained": fl / sus,
+                                   "sustained_source": "profiles/r04_fp64_issue_rates.txt: independent FMAs issue every 4.9 cycles per "
+                                                       "SIMD at the clock the chip holds under them, 0.70 (fp64) / 0.80 (packed fp32) of "
+                                                       "the nominal peak (self-measured: `frac` against the nominal peak is the figure "
+                                                       "of record)",
+                                   "flops_per_pixel_visit": fpp, "pixel_visits": pixel_visits_local, "dtype": args.dtype,
+                                   "flops_source": "tools/count_flops.py on the compiled ISA (profiles/hbm_traffic.json; "
+                                                   "tests/test_dpp_hazard.py holds the file to the tree); every basic block LLVM's loop "
+                                                   "annotations place in the pixel loop, guarded blocks (star spline, own-geometry region) "
+                                                   "included once per visit: a static count, an upper bound of the executed one by the "
+                                                   "rare trips that skip them",
+                                   "instruction_mix": facts.get("instruction_mix_f32" if args.dtype == "f32" else "instruction_mix"),
+                                   "valu_utilization": hbm["valu_utilization"],
+                                   "hbm": hbm,
+                                   "note": "valu_utilization = SQ_ACTIVE_INST_VALU x 4 / SIMD-cycles (hbm.traffic_source says where the "
+                                           "counters come from); the HBM-bound kernel of the path is split_variant.kernel; figures are "
+                                           "rank 0's launch"}
+                out["roofline"]["valu"] = {k: out["roofline"][k] for k in ("achieved", "peak", "unit", "frac", "sustained_fma_peak",
+                                                                           "frac_of_sustained", "flops_per_pixel_visit", "pixel_visits",
+                                                                           "dtype", "instruction_mix")}   # (the rounds-1..4 location)
         if steady is not None:
             out["steady_state"] = steady
         if group_rec is not None:
@@ -794,7 +812,7 @@ def main():
             out["variable_psf"] = variable_psf_record(args, out)
         if extras and args.config == 3 and not args.no_config5 and args.height >= 2048:
             out["config5"] = config5_record(args)
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             tg_cpu = targets if args.config == 3 else targets[:: max(1, S // 2000)]
             out["cpu_baseline"] = cpu_baseline(ctx.problem, fld.vp, tg_cpu)
         sys.stdout.flush()
@@ -833,7 +851,7 @@ def group_main(args):
         raise SystemExit("--driver group over devices %s: only %d visible" % (devices, torch.cuda.device_count()))
     flags = FLAGS_ALL | (cabi.FLAG_FP32 if args.dtype == "f32" else 0)
     if args.config == 3:
-        fld = build_field(args.height, args.width, args.sources, args.seed, variable=args.variable_psf)
+        fld = build_field(args.height, args.width, args.sources, args.seed, cache=False, variable=args.variable_psf)
     else:
         fld = build_multifield(tuple(int(x) for x in args.grid.split(",")), args.height, args.width, args.sources, args.seed)
     out = group_measure(args, fld, devices, flags)
@@ -859,7 +877,7 @@ def group_driver_child(args, devices):
     cmd = [sys.executable, os.path.abspath(__file__), "--driver", "group", "--gpus", str(len(devices)),
            "--group-devices", ",".join(str(d) for d in devices), "--steps", str(args.steps), "--warmup", str(args.warmup),
            "--config", str(args.config), "--dtype", args.dtype, "--height", str(args.height), "--width", str(args.width),
-           "--sources", str(args.sources), "--seed", str(args.seed), "--grid", args.grid, "--no-cpu-baseline"]
+           "--sources", str(args.sources), "--seed", str(args.seed), "--grid", args.grid, "--full", "--no-cpu-baseline"]
     try:
         r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=GROUP_CHILD_TIMEOUT_S)
     except subprocess.TimeoutExpired:
@@ -874,8 +892,8 @@ def group_driver_child(args, devices):
 
 def group_measure(args, fld, devices, flags, check=True):
     """The sweep of `fld` through a celeste_group_t over `devices`: W warm-up sweeps, K timed ones between two
-    celeste_group_sweep_wait, then a pass with HIP-event timing.  Returns the bench line of the group driver (also nested as
-    `group_driver` in the ranks' line at N > 1)."""
+    celeste_group_sweep_wait, then (--full) a pass with HIP-event timing.  Returns the bench line of the group driver (also
+    nested as `group_driver` in the ranks' line at N > 1)."""
     from celeste_jl_amd.group import FieldGroup
     S = len(fld.catalog)
     targets = np.arange(S, dtype=np.int32)
@@ -898,23 +916,19 @@ def group_measure(args, fld, devices, flags, check=True):
         np.savez(os.path.join(args.check_dir, "group.npz"), v=v, d=d)
     if args.dump_outputs and check:      # (the group driver's sweep returns no Hessians: they stay on the members)
         dump_outputs(args.dump_outputs, {"v": v, "d": d, "cnt": cnt})
-    g.enable_timing(True)
-    kms, ev_ms, ga_ms = [], [], []
-    for _ in range(min(20, max(3, args.steps))):
-        g.sweep()
-        g.wait()
-        kms.append(g.last_kernel_ms(0))
-        a, b = g.last_sweep_ms()
-        ev_ms.append(a); ga_ms.append(b)
-    g.enable_timing(False)
-    kms = np.array(kms).mean(axis=0)
-    ev_ms, ga_ms = np.array(ev_ms).mean(axis=0), np.array(ga_ms).mean(axis=0)
+    if args.full:
+        g.enable_timing(True)
+        kms, ev_ms, ga_ms = [], [], []
+        for _ in range(min(20, max(3, args.steps))):
+            g.sweep()
+            g.wait()
+            kms.append(g.last_kernel_ms(0))
+            a, b = g.last_sweep_ms()
+            ev_ms.append(a); ga_ms.append(b)
+        g.enable_timing(False)
+        kms = np.array(kms).mean(axis=0)
+        ev_ms, ga_ms = np.array(ev_ms).mean(axis=0), np.array(ga_ms).mean(axis=0)
     pixel_visits = int(cnt[:, 0].sum())
-    facts = profile_facts() or {}
-    fpp = facts.get("flops_per_pixel_visit_f32" if args.dtype == "f32" else "flops_per_pixel_visit")
-    peak_fl = FP32_VECTOR_PEAK_TFLOPS if args.dtype == "f32" else FP64_VECTOR_PEAK_TFLOPS
-    # member 0's share of the visits (its launch is the one timed), by shard cost
-    visits0 = pixel_visits * costs[0] / max(1, sum(costs))
     n = len(devices)
     enq, aborted = g.collectives()
     out = {"metric": "sources/sec (ELBO value+gradient+Hessian+KL per target source)",
@@ -922,7 +936,7 @@ def group_measure(args, fld, devices, flags, check=True):
            "steps": args.steps, "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True,
            "scaling": "strong", "vs_baseline": None, "dtype": args.dtype, "data": "synthetic",
            "timing_method": "wall clock around K celeste_group_sweep calls between two celeste_group_sweep_wait (all members' "
-                            "streams drained, every catalog gather complete); kernels_ms: HIP events in a pass of its own",
+                            "streams drained, every catalog gather complete)",
            "config": {"workload": ("BASELINE.json configs[%d]: synthetic %dx%dx5 field, %d sources, %s, one process, %d group "
                                    "member(s) on devices %s" % (2 if n == 1 else 3, args.height, args.width, S, args.dtype, n, devices))
                       if args.config == 3 else "BASELINE.json configs[4] through a device group of %d member(s) on %s" % (n, devices),
@@ -932,17 +946,24 @@ def group_measure(args, fld, devices, flags, check=True):
                       "gather_backend": info["exchange"], "members": n, "devices": devices,
                       "collectives_enqueued_per_member": enq, "aborted": aborted,
                       "catalog_gather_bytes_per_step": n * (max(sizes) * 47 + (max(sizes) + 1) // 2) * 8,
-                      "pixel_visits_per_sweep": pixel_visits,
-                      "member_eval_ms": [float(x) for x in ev_ms], "member_gather_ms": [float(x) for x in ga_ms]},
-           "kernels_ms": {"prep": float(kms[0]), "pixel": float(kms[1]), "lift": float(kms[2])}}
-    if fpp:
-        fl = fpp * visits0 / (kms[1] * 1e-3) / 1e12
-        out["roofline"] = {"bound": "fp32_valu" if args.dtype == "f32" else "fp64_valu", "achieved": fl, "peak": peak_fl,
-                           "unit": "TFLOP/s", "frac": fl / peak_fl, "traffic": None, "kernel_ms": float(kms[1]),
-                           "kernel": "pixel_kernel<2, %s>" % ("float" if args.dtype == "f32" else "double"),
-                           "note": "member 0's launch; its share of the pixel visits by shard cost"}
-    if check and not args.no_cpu_baseline and n == 1 and args.config == 3:
-        out["cpu_baseline"] = cpu_baseline(g.problem, fld.vp, targets)
+                      "pixel_visits_per_sweep": pixel_visits}}
+    if args.full:
+        out["timing_method"] += "; kernels_ms: HIP events in a pass of its own"
+        out["config"].update({"member_eval_ms": [float(x) for x in ev_ms], "member_gather_ms": [float(x) for x in ga_ms]})
+        out["kernels_ms"] = {"prep": float(kms[0]), "pixel": float(kms[1]), "lift": float(kms[2])}
+        facts = profile_facts() or {}
+        fpp = facts.get("flops_per_pixel_visit_f32" if args.dtype == "f32" else "flops_per_pixel_visit")
+        peak_fl = FP32_VECTOR_PEAK_TFLOPS if args.dtype == "f32" else FP64_VECTOR_PEAK_TFLOPS
+        # member 0's share of the visits (its launch is the one timed), by shard cost
+        visits0 = pixel_visits * costs[0] / max(1, sum(costs))
+        if fpp:
+            fl = fpp * visits0 / (kms[1] * 1e-3) / 1e12
+            out["roofline"] = {"bound": "fp32_valu" if args.dtype == "f32" else "fp64_valu", "achieved": fl, "peak": peak_fl,
+                               "unit": "TFLOP/s", "frac": fl / peak_fl, "traffic": None, "kernel_ms": float(kms[1]),
+                               "kernel": "pixel_kernel<2, %s>" % ("float" if args.dtype == "f32" else "double"),
+                               "note": "member 0's launch; its share of the pixel visits by shard cost"}
+        if check and not args.no_cpu_baseline and n == 1 and args.config == 3:
+            out["cpu_baseline"] = cpu_baseline(g.problem, fld.vp, targets)
     g.close()
     return out
 
@@ -1123,8 +1144,8 @@ def variable_psf_record(args, head):
     gathered 4 x 4 per pixel (fsm_util.jl:225-248) instead of one 22 KB table per band that never leaves L2 -- swept exactly like
     the headline, as a child run of this script (`--variable-psf`), counters included."""
     import subprocess
-    cmd = [sys.executable, os.path.abspath(__file__), "--variable-psf", "--steps", "100", "--warmup", "5", "--no-cpu-baseline",
-           "--no-extras", "--no-config5", "--height", str(args.height), "--width", str(args.width), "--sources", str(args.sources),
+    cmd = [sys.executable, os.path.abspath(__file__), "--variable-psf", "--steps", "100", "--warmup", "5", "--full",
+           "--no-cpu-baseline", "--no-extras", "--no-config5", "--height", str(args.height), "--width", str(args.width), "--sources", str(args.sources),
            "--seed", str(args.seed)] + (["--no-live-pmc"] if args.no_live_pmc else [])
     env = dict(os.environ)
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
@@ -1163,7 +1184,7 @@ def config5_record(args):
     80 images, 30 000 sources): throughput, the fp32-vs-fp64 check on every source, the fp32 kernel's VALU roofline."""
     import subprocess
     cmd = [sys.executable, os.path.abspath(__file__), "--config", "5", "--dtype", "f32", "--steps", "10", "--warmup", "2",
-           "--kernels-in-pass", "--no-cpu-baseline", "--no-extras", "--shard-projection", "--height", str(args.height),
+           "--full", "--kernels-in-pass", "--no-cpu-baseline", "--no-extras", "--shard-projection", "--height", str(args.height),
            "--width", str(args.width)]
     env = dict(os.environ)
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):

@@ -13,7 +13,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 @pytest.mark.gpu
 def test_bench_json_line():
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--height", "300", "--width", "260",
-                          "--sources", "60", "--steps", "3", "--warmup", "1"], capture_output=True, text=True, timeout=600)
+                          "--sources", "60", "--steps", "3", "--warmup", "1", "--full"], capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1
@@ -60,11 +60,32 @@ def test_bench_json_line():
 
 
 @pytest.mark.gpu
+def test_bench_plain_run_prints_the_headline_only():
+    """without --full the run times its steps and prints the headline: no kernel pass, counters, secondary figures,
+    sub-records or CPU baseline"""
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--height", "300", "--width", "260",
+                          "--sources", "60", "--steps", "3", "--warmup", "1"], capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [ln for ln in out.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
+                "vs_baseline", "dtype", "data", "config", "timing_method", "step_ms"):
+        assert key in d, key
+    assert d["n_gpus"] == 1 and d["steps"] == 3 and d["warmup"] == 1 and d["unit"] == "sources/sec" and d["dtype"] == "f64"
+    assert d["config"]["shard_sizes"] == [60] and abs(d["value"] * d["ms_per_step"] * 1e-3 - 60) < 1e-9 * 60
+    for key in ("roofline", "kernels_ms", "gaps_ms", "context_create_ms", "pixel_visits_per_sec_rank0", "steady_state",
+                "grad_only_sources_per_sec_rank0", "split_variant", "host_api_sources_per_sec", "optimizer", "joint_infer",
+                "shard_projection", "cpu_baseline"):
+        assert key not in d, key
+
+
+@pytest.mark.gpu
 def test_bench_variable_psf_flag():
     """--variable-psf: the same sweep on a field whose PSF is an SDSSPSFMap evaluated at every source -- one stamp per patch, its
     spline coefficients counted per patch in the algorithmic bytes"""
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--height", "300", "--width", "260", "--sources", "60",
-                          "--steps", "3", "--warmup", "1", "--variable-psf", "--no-extras", "--no-cpu-baseline", "--no-live-pmc"],
+                          "--steps", "3", "--warmup", "1", "--variable-psf", "--full", "--no-extras", "--no-cpu-baseline", "--no-live-pmc"],
                          capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     d = json.loads([ln for ln in out.stdout.splitlines() if ln.strip()][-1])
@@ -121,7 +142,7 @@ def test_bench_config5_mode_small_grid():
     """bench.py --config 5: overlapping fields through the sparse patch list, fp32 component loop, the 1e-4 check
     against the fp64 device path inside the run (a 2 x 2 grid of small fields so that it runs in seconds)"""
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--config", "5", "--grid", "2,2", "--height", "260",
-                          "--width", "240", "--sources", "150", "--steps", "3", "--warmup", "1", "--no-cpu-baseline"],
+                          "--width", "240", "--sources", "150", "--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline"],
                          capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-2000:]
     d = json.loads([ln for ln in out.stdout.splitlines() if ln.strip().startswith("{")][0])
@@ -178,6 +199,13 @@ def test_bench_dump_outputs_keeps_to_its_budget(tmp_path):
         assert 0 < len(rows) < len(a) and rows.dtype == np.float64 and np.array_equal(b, a[rows.astype(np.int64)])
         assert np.array_equal(b, np.load(tmp_path / "s2" / (k + ".npy")))
     assert np.array_equal(np.load(tmp_path / "s1" / "v_rows.npy"), np.load(tmp_path / "s1" / "h_rows.npy"))
+
+
+def test_bench_refuses_full_only_options_without_full():
+    """--kernels-in-pass and --shard-projection only shape figures of --full: alone they are refused, not ignored"""
+    for opt in ("--kernels-in-pass", "--shard-projection"):
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), opt], capture_output=True, text=True, timeout=600)
+        assert out.returncode != 0 and "add --full" in out.stderr and "{" not in out.stdout, opt
 
 
 def test_bench_refuses_fewer_than_one_step():

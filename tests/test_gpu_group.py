@@ -384,8 +384,8 @@ def test_bench_group_driver_prints_the_line_and_the_single_rank_catalog(tmp_path
         assert len(lines) == 1                      # RCCL's banner and everything else stay off stdout
         return json.loads(lines[0])
     ref = run(["--no-extras"], "ranks")
-    d1 = run(["--driver", "group"], "g1")
-    d2 = run(["--driver", "group", "--gpus", "2", "--group-devices", "0,0"], "g2")
+    d1 = run(["--driver", "group", "--full"], "g1")
+    d2 = run(["--driver", "group", "--full", "--gpus", "2", "--group-devices", "0,0"], "g2")
     assert d1["n_gpus"] == 1 and d1["ranks_seen"] == 1 and d1["config"]["gather_backend"] == "rccl" and d1["config"]["shard_sizes"] == [60]
     assert d2["config"]["members"] == 2 and d2["config"]["gather_backend"] == "peer_copy" and sum(d2["config"]["shard_sizes"]) == 60
     for d in (d1, d2):

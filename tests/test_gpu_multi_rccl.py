@@ -43,7 +43,7 @@ def _rccl_bench_equals_single_rank(tmp_path, n):
     # the plain form, exactly what the driver types for N = 1: bench.py starts its N ranks itself
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(n), "--backend", "nccl", "--steps", "5",
-                          "--warmup", "2", "--no-extras", "--check-dir", str(tmp_path)], capture_output=True, text=True,
+                          "--warmup", "2", "--full", "--no-extras", "--check-dir", str(tmp_path)], capture_output=True, text=True,
                          timeout=1200, env=env)
     assert res.returncode == 0, res.stderr[-3000:]
     d = json.loads([ln for ln in res.stdout.splitlines() if ln.strip().startswith("{")][0])

@@ -47,7 +47,7 @@ def test_bench_strong_scaling_two_ranks_on_one_gpu_equals_single_rank(tmp_path):
     sys.path.insert(0, ROOT)
     import bench
     shape = ["--height", "420", "--width", "380", "--sources", "180", "--seed", "7"]
-    d = _launch_bench(tmp_path, 2, shape + ["--backend", "gloo", "--steps", "3", "--warmup", "1", "--no-extras",
+    d = _launch_bench(tmp_path, 2, shape + ["--backend", "gloo", "--steps", "3", "--warmup", "1", "--full", "--no-extras",
                                             "--check-dir", str(tmp_path)])
     assert d["n_gpus"] == 2 and d["scaling"] == "strong" and d["config"]["gather_backend"] == "gloo"
     # the same run carries the OTHER driver too: rank 0 alone, one process, two group members (here both on the one device,
@@ -82,7 +82,7 @@ def test_bench_plain_invocation_runs_two_ranks_by_itself(tmp_path):
     import bench
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--height", "420", "--width", "380",
-           "--sources", "180", "--seed", "7", "--steps", "3", "--warmup", "1", "--check-dir", str(tmp_path)]
+           "--sources", "180", "--seed", "7", "--steps", "3", "--warmup", "1", "--full", "--check-dir", str(tmp_path)]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.strip().startswith("{")]
