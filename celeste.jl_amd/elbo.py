@@ -10,7 +10,8 @@
 
 Same names, argument meaning and error behaviour: non-finite parameters or results raise
 AssertionError like the reference's @assert (elbo_objective.jl:487, elbo_args.jl:145-149).
-Sa = 1 is the production configuration (batched, tuned); Sa > 1 goes through celeste_elbo_eval_multi.
+Sa = 1 is the production configuration (batched, tuned); Sa > 1 goes through celeste_elbo_eval_multi, and maximize
+with Sa > 1 through the blend library (celeste_jl_amd.blend).
 """
 import time
 import ctypes as C
@@ -88,6 +89,9 @@ class FieldContext:
         if getattr(self, "_mcmc", None) is not None:
             self._mcmc.close()
             self._mcmc = None
+        if getattr(self, "_blend", None) is not None:
+            self._blend.close()
+            self._blend = None
         if getattr(self, "handle", None):
             self.lib.celeste_ctx_destroy(self.handle)
             self.handle = None
@@ -99,6 +103,14 @@ class FieldContext:
             from .mcmc import MCMCContext
             self._mcmc = MCMCContext(self.problem, self.device)
         return self._mcmc
+
+    # -- blends (libceleste_blend.so, celeste_jl_amd.blend) -------------------------------------------------------------
+    def blend_context(self):
+        """The blend library's copy of this context's problem, created on first use and closed with the context."""
+        if getattr(self, "_blend", None) is None:
+            from .blend import BlendContext
+            self._blend = BlendContext(self.problem, self.device)
+        return self._blend
 
     def mcmc_ais(self, catalog, targets: Sequence[int], cfg=None):
         """run_ais (mcmc_infer.jl:10-135) for every target: one mcmc.MCMCResult per target, in target order."""
@@ -367,12 +379,15 @@ def elbo(ea: ElboArgs, vp, calculate_gradient: bool = True, calculate_hessian: b
 
 
 def maximize(ea: ElboArgs, vp, cfg: Optional[ElboConfig] = None):
-    """ElboMaximize.maximize!(ea, vp, cfg) (ElboMaximize.jl:228-242): optimises the active source in place.
-    Returns (f_evals, max_value, vp) like the reference returns (f_calls, min_value, ...)."""
+    """ElboMaximize.maximize!(ea, vp, cfg) (ElboMaximize.jl:228-242): optimises the active sources in place.
+    Returns (f_evals, max_value, vp) like the reference returns (f_calls, min_value, ...).  Several active sources run as
+    one blend (libceleste_blend.so): one trust-region over all their free parameters."""
     vp_arr = np.asarray(vp, dtype=np.float64).reshape(ea.S, P)
-    if ea.Sa != 1:
-        raise NotImplementedError("maximize! on the device optimises one active source (ParallelRun.jl:482)")
-    new, its, evals, el, _ = ea._ctx.maximize_batch(vp_arr, ea.active_sources, cfg, include_kl=ea.include_kl)
-    a = ea.active_sources[0]
-    vp_arr[a] = new[a]
+    if ea.Sa == 1:
+        new, its, evals, el, _ = ea._ctx.maximize_batch(vp_arr, ea.active_sources, cfg, include_kl=ea.include_kl)
+    else:
+        new, its, evals, el, _ = ea._ctx.blend_context().maximize_blends(vp_arr, [ea.active_sources], cfg,
+                                                                         include_kl=ea.include_kl)
+    for a in ea.active_sources:
+        vp_arr[a] = new[a]
     return int(evals[0]), float(el[0]), vp_arr
