@@ -210,10 +210,16 @@ def _sample_image_job(n):
 
 
 def gen_images(images: List[Image], catalog: List[CatalogEntry], rng: np.random.Generator,
-               expectation: bool = False, workers: int = 1, seed: int = 0) -> None:
+               expectation: bool = False, workers: int = 1, seed: int = 0, device: Optional[int] = None) -> None:
     """Synthetic.gen_images! (Synthetic.jl:30-58).  workers > 1 (many-image problems): the images are rendered by
     forked worker processes and image n is Poisson-sampled from its own generator PCG64([seed, n]) instead of the
-    shared `rng` (the same pixels for any number of workers > 1)."""
+    shared `rng` (the same pixels for any number of workers > 1).
+    device (an integer): the pixels are rendered and sampled on that device (synth.gen_images), image n from Philox
+    stream n of `seed`; `rng` and `workers` are not used.  None: the host path, unchanged."""
+    if device is not None:
+        from . import synth
+        synth.gen_images(images, catalog, seed, expectation=expectation, device=int(device))
+        return
     if workers > 1 and not expectation:
         import multiprocessing as mp
         global _POOL_ARGS
@@ -278,10 +284,13 @@ class Field:
 
 
 def make_field(H: int, W: int, n_sources: int, seed: int, stars_only: bool = False, perturb: bool = True,
-               nan_fraction: float = 0.0, margin: int = 26, name: str = "", variable: bool = False) -> Field:
+               nan_fraction: float = 0.0, margin: int = 26, name: str = "", variable: bool = False,
+               device: Optional[int] = None) -> Field:
     """Configs 2 / 3 of SURVEY.md 8(d): uniform positions with a margin, prior-drawn sources.
     variable=True: SDSS-like varying sky plane, per-row calibration and per-patch PSF stamps (`variable_images`)
-    instead of the constant template of AccuracyBenchmark.make_image."""
+    instead of the constant template of AccuracyBenchmark.make_image.
+    device (an integer): the pixels come from that device, with `seed` as the Philox seed (gen_images); the catalog and the
+    NaN mask are drawn from the host generator as before."""
     rng = np.random.Generator(np.random.PCG64(seed))
     prior = load_prior()
     images = variable_images(H, W, seed) if variable else blank_images(H, W)
@@ -289,7 +298,7 @@ def make_field(H: int, W: int, n_sources: int, seed: int, stars_only: bool = Fal
     for _ in range(n_sources):
         pos = (rng.uniform(margin, H - margin), rng.uniform(margin, W - margin))
         catalog.append(draw_source(prior, rng, pos, force_star=True if stars_only else None))
-    gen_images(images, catalog, rng)
+    gen_images(images, catalog, rng, seed=seed, device=device)
     if nan_fraction > 0:
         for img in images:
             mask = rng.random(img.pixels.shape) < nan_fraction
@@ -304,11 +313,11 @@ def make_field(H: int, W: int, n_sources: int, seed: int, stars_only: bool = Fal
 
 def make_multifield(grid=(2, 2), H: int = 256, W: int = 256, overlap: float = 0.10, n_sources: int = 120,
                     seed: int = 5, perturb: bool = True, margin: int = 8, sparse: bool = False,
-                    workers: int = 1) -> Field:
+                    workers: int = 1, device: Optional[int] = None) -> Field:
     """Config 5 of SURVEY.md 8(d) in miniature: a grid of overlapping fields (5 bands each) on one world
     coordinate system (world = global pixel coordinates; each image has its own affine offset).  A source
     has non-empty patches only in the images it overlaps; the others are the reference's empty boxes
-    (clamp_box, imaged_sources.jl:10-14)."""
+    (clamp_box, imaged_sources.jl:10-14).  device: as in make_field."""
     rng = np.random.Generator(np.random.PCG64(seed))
     prior = load_prior()
     images: List[Image] = []
@@ -323,7 +332,7 @@ def make_multifield(grid=(2, 2), H: int = 256, W: int = 256, overlap: float = 0.
     for _ in range(n_sources):
         pos = (rng.uniform(margin, tot_h - margin), rng.uniform(margin, tot_w - margin))
         catalog.append(draw_source(prior, rng, pos))
-    gen_images(images, catalog, rng, workers=workers, seed=seed)
+    gen_images(images, catalog, rng, workers=workers, seed=seed, device=device)
     patches = get_sky_patches(images, catalog, sparse=sparse)
     nbrs = neighbor_map(patches)
     vp = [catalog_init_source(ce) for ce in catalog]
