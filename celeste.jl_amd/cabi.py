@@ -82,7 +82,7 @@ class CelesteError(RuntimeError):
         self.status = status
 
 
-# every symbol include/celeste_mi355x.h declares
+# every symbol include/celeste_mi355x.h declares (celeste_targets.h, which it includes, holds the prepared-list entry points)
 EXPORTED_SYMBOLS = [
     "celeste_version", "celeste_strerror", "celeste_ctx_create", "celeste_ctx_destroy", "celeste_elbo_eval",
     "celeste_elbo_eval_batch", "celeste_elbo_eval_multi", "celeste_elbo_eval_batch_device", "celeste_ctx_enable_timing",
@@ -96,8 +96,9 @@ EXPORTED_SYMBOLS = [
     "celeste_group_sweep_plan", "celeste_group_sweep", "celeste_group_sweep_wait", "celeste_group_sweep_results",
     "celeste_group_shard_sizes", "celeste_group_enable_timing", "celeste_group_last_sweep_ms", "celeste_group_last_kernel_ms",
     "celeste_group_maximize_batch", "celeste_group_joint_infer", "celeste_group_collectives",
+    "celeste_targets_create", "celeste_targets_create_device", "celeste_targets_destroy", "celeste_elbo_eval_targets_device",
 ]
-ABI_VERSION = 220   # CELESTE_ABI_VERSION of include/celeste_mi355x.h these structs were written against
+ABI_VERSION = 221   # CELESTE_ABI_VERSION of include/celeste_mi355x.h these structs were written against
 
 _lib = None
 
@@ -140,6 +141,11 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.celeste_elbo_eval_batch.argtypes = [vp, c_double_p, C.c_int32, c_int32_p, C.c_uint32, c_double_p,
                                             c_double_p, c_double_p, c_int64_p, c_int32_p]
     lib.celeste_elbo_eval_batch_device.argtypes = [vp, vp, C.c_int32, vp, C.c_uint32, vp, vp, vp, vp, vp, vp]
+    lib.celeste_targets_create.argtypes = [vp, C.c_int32, c_int32_p, C.POINTER(vp)]
+    lib.celeste_targets_create_device.argtypes = [vp, C.c_int32, vp, vp, C.POINTER(vp)]
+    lib.celeste_targets_destroy.argtypes = [vp]
+    lib.celeste_targets_destroy.restype = None
+    lib.celeste_elbo_eval_targets_device.argtypes = [vp, vp, vp, C.c_uint32, vp, vp, vp, vp, vp, vp]
     lib.celeste_ctx_enable_timing.argtypes = [vp, C.c_int]
     lib.celeste_ctx_last_kernel_ms.argtypes = [vp, C.POINTER(C.c_float)]
     lib.celeste_elbo_eval_multi.argtypes = [vp, c_double_p, C.c_int32, c_int32_p, C.c_uint32, C.POINTER(C.c_double),

@@ -195,7 +195,9 @@ struct celeste_ctx {
     int4 *d_vitems_src = nullptr;   // the same, grouped by target
     int32_t *d_vitem_off = nullptr; // S + 1 offsets into d_vitems_src
     std::vector<int32_t> h_vitem_off;
+    std::vector<int32_t> h_vitem_tgt;   // target of every item of d_value_items (prepared target lists pick theirs by it)
     int64_t n_value_items = 0;
+    std::vector<struct celeste_targets *> lists;   // prepared target lists still alive (celeste_targets_create)
     int32_t *d_prep_mark = nullptr; // per source: stamp of the last batch that read its per-image tables
     double *d_lg_sum = nullptr;     // per visit: sum of lgamma(pixel + 1) over the patch's visited pixels
     int64_t *d_nv_base = nullptr;   // visit-list mode: per source, start of its rows in d_nbr_vis
@@ -682,6 +684,8 @@ extern "C" int celeste_ctx_create_on(celeste_images_t *imgs, const celeste_probl
                 desc.push_back(make_int4((int)hv(s2, n), (int)hv(t, n), ch, t));
             }
         c->n_value_items = (int64_t)desc.size();
+        c->h_vitem_tgt.resize(desc.size());
+        for (size_t i = 0; i < desc.size(); ++i) c->h_vitem_tgt[i] = desc[i].w;
         CTX_TRY(dev_upload(&c->d_value_items, desc.data(), desc.size()));
         // the same items grouped by target (joint dataflow launch: an entry renders its own source's neighbours)
         c->h_vitem_off.assign((size_t)c->S + 1, 0);
@@ -717,11 +721,14 @@ extern "C" int celeste_ctx_create_on(celeste_images_t *imgs, const celeste_probl
     return CELESTE_OK;
 } ABI_CATCH
 
+static void targets_free(struct celeste_targets *t);
 extern "C" void celeste_ctx_destroy(celeste_ctx_t *c) {
     if (!c) return;
     (void)hipSetDevice(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     if (c->copy_stream) (void)hipStreamSynchronize(c->copy_stream);
+    for (struct celeste_targets *t : c->lists) targets_free(t);   // (the lists their owners have not destroyed)
+    c->lists.clear();
     void *ptrs[] = {c->d_patches, c->d_coefs, c->d_coefs_f, c->d_bitmaps, c->d_nbr_off, c->d_nbr_idx, c->d_prior,
                     c->d_srcimg, c->d_comps, c->d_geo, c->d_val_off, c->d_val, c->d_needed, c->d_vis_off, c->d_vis_img, c->d_vis_src, c->d_value_items, c->d_vitems_src, c->d_vitem_off, c->d_prep_mark, c->d_rec_off, c->d_lg_sum, c->d_nv_base, c->d_nbr_vis, c->d_items, c->d_work, c->d_work_blk, c->d_work_total, c->d_tile_off, c->d_rec, c->d_acc_split, c->d_acc, c->d_vp, c->d_targets, c->d_v, c->d_d, c->d_h,
                     c->d_cnt, c->d_status};
@@ -829,6 +836,26 @@ static int fused_buffers(celeste_ctx_t *c, size_t n, size_t rec, hipStream_t str
 }
 
 #define VALUE_WIDE_MAX 768     // batches up to this size render the neighbours' light with four wavefronts per item
+// small Hessian-mode fp64 batches run eval_fused_kernel instead of pixel_kernel + lift_kernel; `plain`: none of the
+// launch's optional arguments (active ranks, live count, Hessian slots, render-only) is in use
+static bool want_eval_fused(uint32_t flags, int32_t n_targets, bool plain, const double *d_d, const double *d_h) {
+    const bool can = plain && (flags & CELESTE_FLAG_HESS) && !(flags & (CELESTE_FLAG_FP32 | CELESTE_FLAG_SPLIT)) && d_d && d_h;
+    bool eval_fused = can && n_targets <= EVAL_FUSED_MAX;
+    if (const char *e = getenv("CELESTE_EVAL_FUSED")) {
+        if (atoi(e) == 0) eval_fused = false;
+        else if (atoi(e) == 1) eval_fused = can;
+    }
+    return eval_fused;
+}
+// a workgroup of pixel_kernel handles a group of up to G consecutive chunks of a patch (results do not depend on G, see
+// visit_chunks): 4 for large sweeps, 1 for small batches whose critical path is one patch
+// (measured, round 5: the 2000-target sweep of the bench field 0.499 ms with 2, 0.503 with 1, 0.502 with 3, 0.512 with 4;
+// config 5's 30 000 targets 5.31 ms with 4, 5.45 with 2, 5.30 with 8; a 1000-target shard 0.287 ms with 2, 0.315 with 4)
+static int chunk_group(int32_t n_targets) {
+    int G = n_targets >= 8192 ? 4 : n_targets >= 768 ? 2 : 1;
+    if (const char *e = getenv("CELESTE_CHUNK_GROUP")) if (atoi(e) >= 1 && atoi(e) <= 16) G = atoi(e);
+    return G;
+}
 // render_neighbors = false keeps the neighbours' pre-rendered light of an earlier call (frozen neighbours
 // during an optimisation, ParallelRun.jl:474-488)
 static int launch_eval(celeste_ctx_t *c, const double *d_vp, int32_t n_targets, const int32_t *d_targets,
@@ -896,20 +923,9 @@ static int launch_eval(celeste_ctx_t *c, const double *d_vp, int32_t n_targets, 
         HIP_TRY(hipMalloc((void **)&c->d_work, std::max<size_t>(work_need, 1) * sizeof(int32_t)));
         c->work_cap = work_need;
     }
-    // a workgroup handles a group of up to G consecutive chunks of a patch (results do not depend on G, see
-    // visit_chunks): 4 for large sweeps, 1 for small batches whose critical path is one patch
-    // (measured, round 5: the 2000-target sweep of the bench field 0.499 ms with 2, 0.503 with 1, 0.502 with 3, 0.512 with 4;
-    // config 5's 30 000 targets 5.31 ms with 4, 5.45 with 2, 5.30 with 8; a 1000-target shard 0.287 ms with 2, 0.315 with 4)
-    int G = n_targets >= 8192 ? 4 : n_targets >= 768 ? 2 : 1;
-    if (const char *e = getenv("CELESTE_CHUNK_GROUP")) if (atoi(e) >= 1 && atoi(e) <= 16) G = atoi(e);
+    int G = chunk_group(n_targets);
     // small Hessian-mode fp64 batches: eval_fused_kernel instead of pixel_kernel + lift_kernel (below)
-    bool eval_fused = !render_only && (flags & CELESTE_FLAG_HESS) && !(flags & (CELESTE_FLAG_FP32 | CELESTE_FLAG_SPLIT)) &&
-                      !d_active_rank && !d_live && !d_h_pos && d_d && d_h && n_targets <= EVAL_FUSED_MAX;
-    if (const char *e = getenv("CELESTE_EVAL_FUSED")) {
-        if (atoi(e) == 0) eval_fused = false;
-        else if (atoi(e) == 1) eval_fused = !render_only && (flags & CELESTE_FLAG_HESS) && !(flags & (CELESTE_FLAG_FP32 | CELESTE_FLAG_SPLIT)) &&
-                                          !d_active_rank && !d_live && !d_h_pos && d_d && d_h;
-    }
+    const bool eval_fused = want_eval_fused(flags, n_targets, !render_only && !d_active_rank && !d_live && !d_h_pos, d_d, d_h);
     if (eval_fused) G = 1;        // one record per work item: the work-list total is the batch's number of records
     const int n_classes = WORK_CLASSES;   // work-list classes: full groups, then the patches' last groups by length
     if ((size_t)n_wblk * (n_classes + 1) > c->work_blk_cap) {   // + the row of chunk counts (rec_off)
@@ -1096,6 +1112,206 @@ static int launch_eval(celeste_ctx_t *c, const double *d_vp, int32_t n_targets, 
     HIP_TRY(hipGetLastError());
     return CELESTE_OK;
 }
+
+// ---- prepared target lists -------------------------------------------------------------------------------------------
+// A sweep's work list, record offsets, visit items, target marks and the choice of tables to fill and neighbour items
+// to render depend on (context, target list, chunk size, G) and not on vp.  A caller that evaluates ONE target list
+// again and again (a rank draining its shard: DeviceShardedSweep, celeste_group_sweep) has them made once, by the same
+// kernels, into buffers the list owns; a prepared sweep is then four launches -- SrcGeo + the listed visits' tables (geo_prep_kernel),
+// value_kernel over the listed items, pixel_kernel, lift_kernel -- instead of eight.  Same records in the same order, same
+// arithmetic: the results are those of launch_eval bit for bit.  Nothing of the context's per-call scratch that launch_eval
+// rewrites (d_work, d_rec_off, d_items, d_needed, d_prep_mark, stamp) is touched; d_acc is shared.
+struct celeste_targets {
+    celeste_ctx_t *ctx = nullptr;
+    int32_t n = 0;
+    int G = 1;
+    int32_t *d_targets = nullptr;       // the list's own copy
+    int32_t *d_work = nullptr, *d_work_total = nullptr, *d_rec_off = nullptr;
+    int2 *d_items = nullptr;            // sparse contexts only
+    int32_t *d_needed = nullptr;        // per source: LIST_STAMP for the targets, else 0
+    int32_t *d_visits = nullptr;        // the visits whose tables the list reads: its targets' and their neighbours'
+    int32_t *d_vitems = nullptr;        // the items of the context's d_value_items that belong to the list's targets
+    int64_t n_visits = 0, n_vitems = 0;
+    int64_t n_records = 0;              // chunk records of a sweep (exact)
+    int32_t n_work = 0;                 // work items of pixel_kernel (exact: its grid)
+};
+static const int32_t LIST_STAMP = 1;
+
+static void targets_free(celeste_targets *t) {
+    if (!t) return;
+    void *ptrs[] = {t->d_targets, t->d_work, t->d_work_total, t->d_rec_off, t->d_items, t->d_needed, t->d_visits, t->d_vitems};
+    for (void *p : ptrs) if (p) (void)hipFree(p);
+    delete t;
+}
+
+// targets: host copy of the list, validated by the caller
+static int targets_build(celeste_ctx_t *c, const std::vector<int32_t> &tg, celeste_targets_t **out) {
+    const int32_t n = (int32_t)tg.size();
+    if ((size_t)n * c->M * c->CH > 0x7fffffffull) return CELESTE_ERR_INVALID_ARG;
+    HIP_TRY(hipSetDevice(c->device));
+    celeste_targets *t = new celeste_targets;
+    t->ctx = c; t->n = n; t->G = chunk_group(n);
+    int32_t *d_blk = nullptr;
+    auto fail = [&](int st) { if (d_blk) (void)hipFree(d_blk); (void)hipGetLastError(); targets_free(t); return st; };
+#define LIST_TRY(expr) do { if ((expr) != hipSuccess) return fail(CELESTE_ERR_HIP); } while (0)
+#define LIST_ALLOC(p, bytes) do { if (hipMalloc((void **)&(p), (bytes)) != hipSuccess) return fail(CELESTE_ERR_ALLOC); } while (0)
+    // the compact lists, from the host mirrors: the visits of the targets and of their neighbours (in visit order, as
+    // prep_kernel's grid runs), and the value items of the targets (in the order of d_value_items: longest first)
+    std::vector<char> is_tgt((size_t)c->S, 0), reads((size_t)c->S, 0);
+    for (int32_t s : tg) {
+        is_tgt[s] = 1; reads[s] = 1;
+        for (int64_t q = c->h_nbr_off[s]; q < c->h_nbr_off[s + 1]; ++q) reads[c->h_nbr_idx[q]] = 1;
+        t->n_records += c->h_src_chunks[s];
+    }
+    std::vector<int32_t> visits, vitems;
+    for (int s = 0; s < c->S; ++s)
+        if (reads[s]) for (int v = c->h_vis_off[s]; v < c->h_vis_off[s + 1]; ++v) visits.push_back(v);
+    for (size_t i = 0; i < c->h_vitem_tgt.size(); ++i) if (is_tgt[c->h_vitem_tgt[i]]) vitems.push_back((int32_t)i);
+    t->n_visits = (int64_t)visits.size(); t->n_vitems = (int64_t)vitems.size();
+    const int n_cand = n * c->M;                                 // candidate visits k = ti * M + j
+    const int n_wblk = (n_cand + WORK_NT - 1) / WORK_NT;
+    const size_t n_blk = (size_t)n_wblk * (WORK_CLASSES + 1);
+    LIST_ALLOC(t->d_targets, (size_t)n * sizeof(int32_t));
+    LIST_ALLOC(t->d_work, std::max<size_t>((size_t)t->n_records, 1) * sizeof(int32_t));
+    LIST_ALLOC(t->d_work_total, sizeof(int32_t));
+    LIST_ALLOC(t->d_rec_off, (size_t)n_cand * sizeof(int32_t));
+    if (!c->dense) LIST_ALLOC(t->d_items, (size_t)n_cand * sizeof(int2));
+    LIST_ALLOC(t->d_needed, (size_t)c->S * sizeof(int32_t));
+    LIST_ALLOC(t->d_visits, std::max<size_t>(visits.size(), 1) * sizeof(int32_t));
+    LIST_ALLOC(t->d_vitems, std::max<size_t>(vitems.size(), 1) * sizeof(int32_t));
+    LIST_ALLOC(d_blk, n_blk * sizeof(int32_t));
+    LIST_TRY(hipMemcpy(t->d_targets, tg.data(), (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice));
+    if (!visits.empty()) LIST_TRY(hipMemcpy(t->d_visits, visits.data(), visits.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+    if (!vitems.empty()) LIST_TRY(hipMemcpy(t->d_vitems, vitems.data(), vitems.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+    LIST_TRY(hipMemset(t->d_needed, 0, (size_t)c->S * sizeof(int32_t)));
+    // the half of setup_thread that depends on the targets alone (vp == nullptr: no SrcGeo): visit items and target marks
+    const size_t setup_threads = (size_t)n * (c->dense ? 1 : c->M);
+    hipLaunchKernelGGL(setup_kernel, dim3((unsigned)((setup_threads + 63) / 64)), dim3(64), 0, nullptr, (const double *)nullptr, -1,
+                       (SrcGeo *)nullptr, t->d_targets, n, c->d_vis_off, c->d_vis_img, c->M, t->d_items, t->d_needed, LIST_STAMP,
+                       (int32_t *)nullptr, c->d_nbr_off, c->d_nbr_idx, (const int32_t *)nullptr);
+    hipLaunchKernelGGL(work_count_kernel, dim3(n_wblk), dim3(WORK_NT), 0, nullptr, t->d_targets, n_cand, c->d_patches,
+                       c->d_vis_off, c->d_vis_img, c->N, c->M, c->chunk_px, t->G, (int)c->dense, d_blk, (const int32_t *)nullptr);
+    hipLaunchKernelGGL(work_scan_kernel, dim3(1), dim3(1024), 0, nullptr, d_blk, (int)n_blk, t->d_work_total, n_wblk * WORK_CLASSES);
+    hipLaunchKernelGGL(work_fill_kernel, dim3(n_wblk), dim3(WORK_NT), 0, nullptr, t->d_targets, n_cand, c->d_patches,
+                       c->d_vis_off, c->d_vis_img, c->N, c->M, c->CH, c->chunk_px, t->G, (int)c->dense, d_blk, t->d_work,
+                       (const int32_t *)nullptr, t->d_rec_off);
+    LIST_TRY(hipGetLastError());
+    LIST_TRY(hipMemcpy(&t->n_work, t->d_work_total, sizeof(int32_t), hipMemcpyDeviceToHost));   // (waits for the kernels)
+    LIST_TRY(hipFree(d_blk)); d_blk = nullptr;
+#undef LIST_TRY
+#undef LIST_ALLOC
+    if (t->n_work < 0 || (int64_t)t->n_work > t->n_records) return fail(CELESTE_ERR_HIP);   // (a group holds at least one record)
+    c->lists.push_back(t);
+    *out = t;
+    return CELESTE_OK;
+}
+
+extern "C" int celeste_targets_create(celeste_ctx_t *c, int32_t n_targets, const int32_t *targets, celeste_targets_t **out) try {
+    if (!c || !out || !targets || n_targets <= 0) return CELESTE_ERR_INVALID_ARG;
+    *out = nullptr;
+    for (int32_t i = 0; i < n_targets; ++i) if (targets[i] < 0 || targets[i] >= c->S) return CELESTE_ERR_INVALID_ARG;
+    return targets_build(c, std::vector<int32_t>(targets, targets + n_targets), out);
+} ABI_CATCH
+
+extern "C" int celeste_targets_create_device(celeste_ctx_t *c, int32_t n_targets, const int32_t *d_targets, void *stream_,
+                                             celeste_targets_t **out) try {
+    if (!c || !out || !d_targets || n_targets <= 0) return CELESTE_ERR_INVALID_ARG;
+    *out = nullptr;
+    HIP_TRY(hipSetDevice(c->device));
+    std::vector<int32_t> tg((size_t)n_targets);
+    HIP_TRY(hipMemcpyAsync(tg.data(), d_targets, (size_t)n_targets * sizeof(int32_t), hipMemcpyDeviceToHost, (hipStream_t)stream_));
+    HIP_TRY(hipStreamSynchronize((hipStream_t)stream_));      // (what the caller queued on `stream` has written the list)
+    for (int32_t s : tg) if (s < 0 || s >= c->S) return CELESTE_ERR_INVALID_ARG;
+    return targets_build(c, tg, out);
+} ABI_CATCH
+
+// the list leaves its context and is freed; the caller has made the list's device current and knows no sweep over it in flight
+static void targets_release(celeste_targets_t *t) {
+    celeste_ctx_t *c = t->ctx;
+    auto it = std::find(c->lists.begin(), c->lists.end(), t);
+    if (it != c->lists.end()) c->lists.erase(it);
+    targets_free(t);
+}
+
+extern "C" void celeste_targets_destroy(celeste_targets_t *t) {
+    if (!t) return;
+    (void)hipSetDevice(t->ctx->device);
+    (void)hipDeviceSynchronize();        // (a sweep over the list may be in flight on any stream)
+    targets_release(t);
+}
+
+// A sweep over a prepared list.  What the prepared path does not serve goes to launch_eval with the list's own copy of the
+// targets: single precision (its 512-pixel chunks need lists of their own), the split variant, batches small enough for
+// eval_fused_kernel, CELESTE_NO_PREPARED=1 (the A/B switch).
+static int launch_prepared(celeste_ctx_t *c, const celeste_targets_t *t, const double *d_vp, uint32_t flags, double *d_v,
+                           double *d_d, double *d_h, int64_t *d_counters, int32_t *d_status, void *stream_) {
+    if (!c || !t || t->ctx != c) return CELESTE_ERR_INVALID_ARG;
+    const int32_t n_targets = t->n;
+    const char *off = getenv("CELESTE_NO_PREPARED");
+    if ((off && atoi(off) != 0) || (flags & (CELESTE_FLAG_FP32 | CELESTE_FLAG_SPLIT)) ||
+        want_eval_fused(flags, n_targets, true, d_d, d_h))
+        return launch_eval(c, d_vp, n_targets, t->d_targets, flags, d_v, d_d, d_h, d_counters, d_status, stream_, true, nullptr,
+                           t->n_records);    // (the list knows its chunk count)
+    if (!d_vp || !d_v || !d_status) return CELESTE_ERR_INVALID_ARG;
+    if ((flags & CELESTE_FLAG_HESS) && !d_h) return CELESTE_ERR_INVALID_ARG;
+    if ((flags & (CELESTE_FLAG_GRAD | CELESTE_FLAG_HESS)) && !d_d) return CELESTE_ERR_INVALID_ARG;
+    hipStream_t stream = (hipStream_t)stream_;
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t need = std::max<size_t>((size_t)t->n_records, 1) * ACC_N;
+    if (need > c->acc_cap) {
+        if (c->d_acc) { HIP_TRY(hipStreamSynchronize(stream)); HIP_TRY(hipFree(c->d_acc)); c->d_acc = nullptr; }
+        HIP_TRY(hipMalloc((void **)&c->d_acc, need * sizeof(double)));
+        c->acc_cap = need;
+    }
+    const int CH = c->CH, chunk_px = c->chunk_px;
+    if (c->timing) HIP_TRY(hipEventRecord(c->ev[0], stream));
+    // SrcGeo of every source (64 per workgroup) and the tables of the listed visits, side by side in one launch
+    const unsigned geo_blocks = (unsigned)((c->S + 63) / 64);
+    hipLaunchKernelGGL(geo_prep_kernel, dim3(geo_blocks + (unsigned)t->n_visits), dim3(64), 0, stream, d_vp, c->d_images,
+                       c->d_patches, c->d_vis_src, c->d_vis_img, c->K, c->d_srcimg, c->d_comps, t->d_visits, (int)geo_blocks,
+                       c->S, c->d_geo);
+    if (t->n_vitems > 0) {
+        const bool wide_items = n_targets <= VALUE_WIDE_MAX && c->chunk_px == 256 && !getenv("CELESTE_NO_WIDE_VALUE");
+#define LAUNCH_VALUE(WAVES)                                                                                                 \
+        hipLaunchKernelGGL((value_kernel<double, WAVES>), dim3((unsigned)t->n_vitems), dim3(64 * WAVES), 0, stream,        \
+                           c->d_patches, c->d_coefs, c->d_srcimg, c->d_comps, t->d_needed, LIST_STAMP, c->d_val_off,        \
+                           c->d_value_items, c->NC, c->chunk_px, c->d_val, c->d_coefs_f, t->d_vitems)
+        if (wide_items) LAUNCH_VALUE(4); else LAUNCH_VALUE(1);
+#undef LAUNCH_VALUE
+    }
+    if (c->timing) HIP_TRY(hipEventRecord(c->ev[1], stream));
+    const dim3 grid((unsigned)std::max<int32_t>(t->n_work, 1));
+#define LAUNCH_PIXEL(MODE)                                                                                                  \
+    hipLaunchKernelGGL((pixel_kernel<MODE, double>), grid, dim3(64), 0, stream, c->d_images, c->d_patches, c->d_coefs,      \
+                       c->d_bitmaps, c->d_srcimg, c->d_comps, c->d_nbr_off, c->d_nbr_idx, c->d_val_off, c->d_val,           \
+                       t->d_targets, c->N, c->NC, CH, chunk_px, t->G, c->d_acc, c->d_tile_off, c->d_rec,                    \
+                       (const int32_t *)nullptr, t->d_items, c->M, t->d_work, t->d_work_total, c->d_nv_base, c->d_nbr_vis,  \
+                       t->d_rec_off, c->d_coefs_f)
+    if (flags & CELESTE_FLAG_HESS) LAUNCH_PIXEL(2);
+    else if (flags & CELESTE_FLAG_GRAD) LAUNCH_PIXEL(1);
+    else LAUNCH_PIXEL(0);
+#undef LAUNCH_PIXEL
+    if (c->timing) HIP_TRY(hipEventRecord(c->ev[2], stream));
+    c->ev_split = 0;
+    const int lift_nt = n_targets <= 1024 ? 512 : 256;     // (as launch_eval)
+    bool lift7 = n_targets > 4096;
+    if (const char *e = getenv("CELESTE_LIFT_WAVES")) lift7 = atoi(e) == 7;
+#define LIFT_ARGS dim3(n_targets), dim3(lift_nt), 0, stream, d_vp, c->d_images, c->d_patches, c->d_geo, c->d_nbr_off,       \
+                  c->d_nbr_idx, t->d_targets, c->d_acc, c->d_prior, c->d_vis_off, c->d_vis_img, c->N, c->M, CH, chunk_px,   \
+                  flags, d_v, d_d, d_h, d_counters, d_status, (const int32_t *)nullptr, c->d_lg_sum, t->d_rec_off, \
+                  (const int32_t *)nullptr
+    if (lift7) hipLaunchKernelGGL(lift_kernel<7>, LIFT_ARGS); else hipLaunchKernelGGL(lift_kernel<8>, LIFT_ARGS);
+#undef LIFT_ARGS
+    if (c->timing) { HIP_TRY(hipEventRecord(c->ev[3], stream)); c->ev_valid = 1; }
+    HIP_TRY(hipGetLastError());
+    return CELESTE_OK;
+}
+
+extern "C" int celeste_elbo_eval_targets_device(celeste_ctx_t *c, const celeste_targets_t *t, const double *d_vp, uint32_t flags,
+                                                double *d_v, double *d_d, double *d_h, int64_t *d_counters,
+                                                int32_t *d_status, void *stream_) try {
+    return launch_prepared(c, t, d_vp, flags, d_v, d_d, d_h, d_counters, d_status, stream_);
+} ABI_CATCH
 
 // ---- a copy stream whose copies really run beside the kernels -------------------------------------------------------
 // HIP maps streams onto a few hardware queues in the order of their first use, and what else a queue carries decides

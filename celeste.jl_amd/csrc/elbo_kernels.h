@@ -174,6 +174,7 @@ __device__ __forceinline__ void prep_visit(int c, int s, int n, int sn, const do
     brightness_moments_wave(c, vs, p, b, srcimg + sn);
 }
 
+__device__ inline void source_geo(const double *vp, int s, SrcGeo *geo);
 __global__ void __launch_bounds__(64)
 prep_kernel(const double *__restrict__ vp, const DevImage *__restrict__ images,
             const DevPatch *__restrict__ patches, const int32_t *__restrict__ vis_src,
@@ -205,6 +206,24 @@ prep_kernel(const double *__restrict__ vp, const DevImage *__restrict__ images,
         if (mark && mark[s] != stamp) return;
     }
     prep_visit(threadIdx.x, s, n, sn, vp, images, patches, K, srcimg, comps);
+}
+
+// prep_kernel over an index array -- workgroup b fills the tables of visit visit_list[b], the visits a prepared target list
+// reads (celeste_targets_t), found once per list instead of marked once per sweep -- with setup_kernel's SrcGeo half as the
+// first geo_blocks workgroups, 64 sources each: nothing in the launch reads `geo`, so the two parts run side by side and a
+// prepared sweep is one launch shorter.  A kernel of its own and not a mode of prep_kernel: SrcGeo's sincos takes 92
+// VGPRs against prep_kernel's 34, which every other caller of prep_kernel keeps.
+__global__ void __launch_bounds__(64)
+geo_prep_kernel(const double *__restrict__ vp, const DevImage *__restrict__ images, const DevPatch *__restrict__ patches,
+                const int32_t *__restrict__ vis_src, const int32_t *__restrict__ vis_img, int K, SrcImg *__restrict__ srcimg,
+                Comp *__restrict__ comps, const int32_t *__restrict__ visit_list, int geo_blocks, int S, SrcGeo *__restrict__ geo) {
+    if ((int)blockIdx.x < geo_blocks) {
+        const int k = blockIdx.x * 64 + threadIdx.x;
+        if (k < S) source_geo(vp, k, geo);
+        return;
+    }
+    const int sn = visit_list[(int)blockIdx.x - geo_blocks];
+    prep_visit(threadIdx.x, vis_src[sn], vis_img[sn], sn, vp, images, patches, K, srcimg, comps);
 }
 
 // per-source shape derivatives and the finiteness flag of its parameters
@@ -623,7 +642,9 @@ __device__ inline void setup_thread(int k, const double *__restrict__ vp, int S,
     // S < 0: the neighbours are frozen (an optimiser iteration) -- only the targets have moved since the batch's SrcGeo
     // table was made, and the neighbours' entries (their finiteness flags) keep describing the parameters they were
     // rendered with
-    if (S < 0) { if (k < n_targets) source_geo(vp, targets[k], geo); }
+    // vp == nullptr: no SrcGeo at all -- the half of this function that depends on the targets alone (a prepared list)
+    if (!vp) { }
+    else if (S < 0) { if (k < n_targets) source_geo(vp, targets[k], geo); }
     else if (k < S) source_geo(vp, k, geo);
     if (prep_mark && k < n_targets) {   // the sources whose per-image tables this batch reads
         const int t = targets[k];
@@ -1085,7 +1106,9 @@ value_kernel(const DevPatch *__restrict__ patches, const double *__restrict__ co
              const SrcImg *__restrict__ srcimg, const Comp *__restrict__ comps,
              const int32_t *__restrict__ is_target, int32_t stamp, const int64_t *__restrict__ val_off,
              const int4 *__restrict__ items, int NC, int chunk_px, double2 *__restrict__ val,
-             const float *__restrict__ coefs_f) {
+             const float *__restrict__ coefs_f, const int32_t *__restrict__ item_list = nullptr) {
+    // item_list (optional): workgroup b renders item item_list[b] -- the items of a prepared target list's targets
+    // (celeste_targets_t), in the order of `items`, instead of every item of the context tested against the marks
     __shared__ double etab[64];
 #ifdef VALUE_TIMING
     long long vts[4]; vts[0] = clock64();     // stamps only; the (contended) atomics all come at the very end
@@ -1095,7 +1118,7 @@ value_kernel(const DevPatch *__restrict__ patches, const double *__restrict__ co
 #endif
     // an item = {table index of the neighbour's (source, image) entry, of the target's, chunk, target}: one 16-byte
     // load instead of a chain link -> source, link -> neighbour, item -> image | chunk
-    const int4 it = items[blockIdx.x];
+    const int4 it = items[item_list ? item_list[blockIdx.x] : blockIdx.x];
     const int sn = it.x, ch = it.z, t = it.w;
     if (is_target[t] != stamp) return;
     const DevPatch &P = patches[sn];

@@ -76,6 +76,7 @@ struct GroupMember {
     // device
     double *d_vp = nullptr, *d_vp_nbr = nullptr, *d_entry = nullptr;   // S x 44 tables
     int32_t *d_targets = nullptr, *d_idx = nullptr;     // the shard's targets; their positions in the caller's list
+    celeste_targets_t *plan_list = nullptr;             // the shard of the current sweep plan as a prepared list (celeste_group_sweep)
     double *d_pos = nullptr;
     int32_t *d_it = nullptr, *d_ev = nullptr, *d_st = nullptr;
     double *d_el = nullptr;
@@ -621,6 +622,8 @@ static int group_plan_locked(celeste_group *g, const double *vp, int32_t n_targe
     int rc = group_run(g, [&](GroupMember *m) -> int {
         HIP_TRY(hipSetDevice(m->device));
         hipStream_t st = m->ctx->stream;
+        // the earlier plan's prepared list (its sweeps were drained above)
+        if (m->plan_list) { targets_release(m->plan_list); m->plan_list = nullptr; }
         int s1 = group_target_buffers(m, m->tg.size());
         if (s1 != CELESTE_OK) return s1;
         const size_t blk = g->plan_blk;
@@ -653,7 +656,16 @@ extern "C" int celeste_group_sweep_plan(celeste_group_t *g, const double *vp, in
     if (!g || !vp || n_targets < 1 || (flags & (CELESTE_FLAG_SPLIT))) return CELESTE_ERR_INVALID_ARG;
     if (group_check_targets(g, n_targets, targets) != CELESTE_OK) return CELESTE_ERR_INVALID_ARG;
     std::lock_guard<std::mutex> lock(g->call_mu);
-    return group_plan_locked(g, vp, n_targets, targets, flags);
+    int rc = group_plan_locked(g, vp, n_targets, targets, flags);
+    if (rc != CELESTE_OK) return rc;
+    // the plan's shards are swept again and again: each member's as a prepared list (what depends on the targets alone is
+    // made here, once, instead of by every sweep)
+    rc = group_run(g, [&](GroupMember *m) -> int {
+        // (single precision sweeps its own 512-pixel chunks: a list would serve nothing there)
+        return m->tg.empty() || (flags & CELESTE_FLAG_FP32) ? CELESTE_OK : celeste_targets_create(m->ctx, (int32_t)m->tg.size(), m->tg.data(), &m->plan_list);
+    });
+    if (rc != CELESTE_OK) g->planned = false;
+    return rc;
 } ABI_CATCH
 
 // One sweep of the member's shard into block k, then the catalog gather on the second stream.  Whatever fails in front of the
@@ -668,9 +680,13 @@ static int group_sweep_member(celeste_group *g, GroupMember *m, int k) {
     int own_rc = CELESTE_OK;
     if (group_fault(g, m, GROUP_FAULT_LAUNCH)) own_rc = CELESTE_ERR_HIP;
     else if (!m->tg.empty())
-        own_rc = launch_eval(m->ctx, m->d_vp, (int32_t)m->tg.size(), m->d_targets, g->plan_flags, blk, blk + W, m->d_h,
-                             reinterpret_cast<int64_t *>(blk + (size_t)W * (1 + CEL_P)),
-                             reinterpret_cast<int32_t *>(blk + (size_t)W * (1 + CEL_P + 2)), st, true, nullptr, m->n_chunks);
+        own_rc = m->plan_list
+            ? launch_prepared(m->ctx, m->plan_list, m->d_vp, g->plan_flags, blk, blk + W, m->d_h,
+                              reinterpret_cast<int64_t *>(blk + (size_t)W * (1 + CEL_P)),
+                              reinterpret_cast<int32_t *>(blk + (size_t)W * (1 + CEL_P + 2)), st)
+            : launch_eval(m->ctx, m->d_vp, (int32_t)m->tg.size(), m->d_targets, g->plan_flags, blk, blk + W, m->d_h,
+                          reinterpret_cast<int64_t *>(blk + (size_t)W * (1 + CEL_P)),
+                          reinterpret_cast<int32_t *>(blk + (size_t)W * (1 + CEL_P + 2)), st, true, nullptr, m->n_chunks);
     // (a member whose launch failed still takes part in the gather -- the collective needs every rank, and the others' sweeps
     // are sound; the call reports this member's error)
     if (g->timing) HIP_TRY(hipEventRecord(m->t1, st));

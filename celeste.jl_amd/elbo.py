@@ -65,6 +65,7 @@ class FieldContext:
             cabi.check(self.lib.celeste_ctx_create_on(image_set.handle, C.byref(self.problem.c), C.byref(h)), self.lib)
         self.create_ms = (time.perf_counter() - t0) * 1e3   # the C call alone: uploads, stamp conditioning + prefilter, tables
         self.handle = h
+        self._prepared = {}     # (device pointer, n) -> celeste_targets_t handle (prepare_targets)
 
     @classmethod
     def from_catalog(cls, images, catalog, psf_K: int = 2, prior: Optional[dict] = None, device: int = 0,
@@ -93,6 +94,9 @@ class FieldContext:
             self._blend.close()
             self._blend = None
         if getattr(self, "handle", None):
+            for h in getattr(self, "_prepared", {}).values():
+                self.lib.celeste_targets_destroy(h)
+            self._prepared = {}
             self.lib.celeste_ctx_destroy(self.handle)
             self.handle = None
 
@@ -192,8 +196,36 @@ class FieldContext:
         return (v.value, d.reshape(sa, P).T.copy() if want_d else None, h, np.array([na.value, ni.value]))
 
     # -- device-pointer API (torch tensors or raw pointers) -----------------------------------
+    def prepare_targets(self, d_targets: int, n_targets: int, stream: int = 0):
+        """Register the device-resident target list (d_targets, n_targets) as a prepared list (celeste_targets_t): what
+        a sweep derives from the targets alone is made now, once, and `eval_batch_device` calls with this very pointer
+        and count run the shorter prepared sweep -- same results.  The library copies the list, so the caller must not
+        write the array while it is registered (a changed array would still be evaluated as it was): `forget_targets`
+        drops the registration, `close` drops them all.  Returns the handle."""
+        key = (int(d_targets), int(n_targets))
+        self.forget_targets(*key)       # (registered again: the array may hold another list by now)
+        h = C.c_void_p()
+        cabi.check(self.lib.celeste_targets_create_device(self.handle, n_targets, d_targets, stream, C.byref(h)), self.lib)
+        self._prepared[key] = h
+        return h
+
+    def forget_targets(self, d_targets: int, n_targets: int):
+        h = self._prepared.pop((int(d_targets), int(n_targets)), None)
+        if h is not None:
+            self.lib.celeste_targets_destroy(h)
+
+    def eval_targets_device(self, handle, d_vp: int, flags: int, d_v: int, d_d: int, d_h: int, d_counters: int,
+                            d_status: int, stream: int = 0):
+        """`eval_batch_device` over a prepared list (the handle of `prepare_targets`)."""
+        cabi.check(self.lib.celeste_elbo_eval_targets_device(self.handle, handle, d_vp, flags, d_v, d_d, d_h, d_counters,
+                                                             d_status, stream), self.lib)
+
     def eval_batch_device(self, d_vp: int, n_targets: int, d_targets: int, flags: int, d_v: int, d_d: int,
                           d_h: int, d_counters: int, d_status: int, stream: int = 0):
+        if self._prepared:
+            h = self._prepared.get((int(d_targets), int(n_targets)))
+            if h is not None:
+                return self.eval_targets_device(h, d_vp, flags, d_v, d_d, d_h, d_counters, d_status, stream)
         cabi.check(self.lib.celeste_elbo_eval_batch_device(self.handle, d_vp, n_targets, d_targets, flags, d_v, d_d,
                                                            d_h, d_counters, d_status, stream), self.lib)
 

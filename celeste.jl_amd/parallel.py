@@ -173,9 +173,24 @@ class DeviceShardedSweep:
             elif self.gather:
                 self.h_block = torch.zeros(W * (1 + P), dtype=torch.float64).pin_memory()
                 self.gathered = torch.zeros(world * W * (1 + P), dtype=torch.float64)
+        # the shard is swept again and again and d_tg is never written: what a sweep derives from the targets alone is
+        # made once (FieldContext.prepare_targets); step()'s eval_batch_device then finds the list by (pointer, n)
+        if self.n > 0 and hasattr(ctx, "prepare_targets"):
+            ctx.prepare_targets(self.d_tg.data_ptr(), self.n, self.compute_stream.cuda_stream)
         self.k = 0
         self.last = 0
         self.gather_bytes = world * W * (1 + P) * 8 if self.gather else 0
+
+    def close(self):
+        """Drop the registration of this sweep's target list (its memory may be reused for another list)."""
+        if self.n > 0 and getattr(self.ctx, "handle", None) and hasattr(self.ctx, "forget_targets"):
+            self.ctx.forget_targets(self.d_tg.data_ptr(), self.n)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
     def step(self, d_vp_ptr: int):
         """One sweep: evaluate this rank's shard against the parameter table at device pointer `d_vp_ptr`

