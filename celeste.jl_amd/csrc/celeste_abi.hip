@@ -19,6 +19,7 @@
 #include "optim_kernels.h"
 #include "fused_kernels.h"
 #include "host_tables.h"
+#include "value_union.h"
 
 struct celeste_group;
 
@@ -196,6 +197,7 @@ struct celeste_ctx {
     int32_t *d_vitem_off = nullptr; // S + 1 offsets into d_vitems_src
     std::vector<int32_t> h_vitem_off;
     std::vector<int32_t> h_vitem_tgt;   // target of every item of d_value_items (prepared target lists pick theirs by it)
+    std::vector<ValueUnionLink> h_vitem_link;   // ... and its {neighbour's visit, target's visit} (value_union_build)
     int64_t n_value_items = 0;
     std::vector<struct celeste_targets *> lists;   // prepared target lists still alive (celeste_targets_create)
     int32_t *d_prep_mark = nullptr; // per source: stamp of the last batch that read its per-image tables
@@ -685,7 +687,8 @@ extern "C" int celeste_ctx_create_on(celeste_images_t *imgs, const celeste_probl
             }
         c->n_value_items = (int64_t)desc.size();
         c->h_vitem_tgt.resize(desc.size());
-        for (size_t i = 0; i < desc.size(); ++i) c->h_vitem_tgt[i] = desc[i].w;
+        c->h_vitem_link.resize(desc.size());
+        for (size_t i = 0; i < desc.size(); ++i) { c->h_vitem_tgt[i] = desc[i].w; c->h_vitem_link[i] = {desc[i].x, desc[i].y}; }
         CTX_TRY(dev_upload(&c->d_value_items, desc.data(), desc.size()));
         // the same items grouped by target (joint dataflow launch: an entry renders its own source's neighbours)
         c->h_vitem_off.assign((size_t)c->S + 1, 0);
@@ -1118,8 +1121,8 @@ static int launch_eval(celeste_ctx_t *c, const double *d_vp, int32_t n_targets, 
 // to render depend on (context, target list, chunk size, G) and not on vp.  A caller that evaluates ONE target list
 // again and again (a rank draining its shard: DeviceShardedSweep, celeste_group_sweep) has them made once, by the same
 // kernels, into buffers the list owns; a prepared sweep is then four launches -- SrcGeo + the listed visits' tables (geo_prep_kernel),
-// value_kernel over the listed items, pixel_kernel, lift_kernel -- instead of eight.  Same records in the same order, same
-// arithmetic: the results are those of launch_eval bit for bit.  Nothing of the context's per-call scratch that launch_eval
+// value_union_kernel over the list's neighbour pixels (each once: value_union.h), pixel_kernel, lift_kernel -- instead of
+// eight.  Same records in the same order, same arithmetic: the results are those of launch_eval bit for bit.  Nothing of the context's per-call scratch that launch_eval
 // rewrites (d_work, d_rec_off, d_items, d_needed, d_prep_mark, stamp) is touched; d_acc is shared.
 struct celeste_targets {
     celeste_ctx_t *ctx = nullptr;
@@ -1131,7 +1134,10 @@ struct celeste_targets {
     int32_t *d_needed = nullptr;        // per source: LIST_STAMP for the targets, else 0
     int32_t *d_visits = nullptr;        // the visits whose tables the list reads: its targets' and their neighbours'
     int32_t *d_vitems = nullptr;        // the items of the context's d_value_items that belong to the list's targets
-    int64_t n_visits = 0, n_vitems = 0;
+    // the same pixels, each once (value_union.h): what a sweep renders; d_vitems is the A/B switch's (CELESTE_NO_VALUE_UNION=1)
+    int4 *d_uitems = nullptr;           // {neighbour's visit, first, count, trips}, longest first
+    int32_t *d_upx = nullptr;           // per wanted pixel: its offset in the neighbour's patch buffer (4 B per pixel)
+    int64_t n_visits = 0, n_vitems = 0, n_uitems = 0;
     int64_t n_records = 0;              // chunk records of a sweep (exact)
     int32_t n_work = 0;                 // work items of pixel_kernel (exact: its grid)
 };
@@ -1139,7 +1145,8 @@ static const int32_t LIST_STAMP = 1;
 
 static void targets_free(celeste_targets *t) {
     if (!t) return;
-    void *ptrs[] = {t->d_targets, t->d_work, t->d_work_total, t->d_rec_off, t->d_items, t->d_needed, t->d_visits, t->d_vitems};
+    void *ptrs[] = {t->d_targets, t->d_work, t->d_work_total, t->d_rec_off, t->d_items, t->d_needed, t->d_visits, t->d_vitems,
+                    t->d_uitems, t->d_upx};
     for (void *p : ptrs) if (p) (void)hipFree(p);
     delete t;
 }
@@ -1167,7 +1174,19 @@ static int targets_build(celeste_ctx_t *c, const std::vector<int32_t> &tg, celes
     for (int s = 0; s < c->S; ++s)
         if (reads[s]) for (int v = c->h_vis_off[s]; v < c->h_vis_off[s + 1]; ++v) visits.push_back(v);
     for (size_t i = 0; i < c->h_vitem_tgt.size(); ++i) if (is_tgt[c->h_vitem_tgt[i]]) vitems.push_back((int32_t)i);
-    t->n_visits = (int64_t)visits.size(); t->n_vitems = (int64_t)vitems.size();
+    // the pixels of those items' rectangles, each once, and the items over them (value_union.h)
+    std::vector<int32_t> upx;
+    std::vector<ValueUnionItem> uitems;
+    {
+        static_assert(sizeof(ValueUnionBox) == 4 * sizeof(int32_t) && sizeof(ValueUnionItem) == sizeof(int4), "layout");
+        std::vector<ValueUnionBox> boxes(c->h_patches.size());
+        for (size_t v = 0; v < boxes.size(); ++v) { const DevPatch &q = c->h_patches[v]; boxes[v] = {q.off_h, q.off_w, q.H2, q.W2}; }
+        std::vector<ValueUnionLink> links;
+        links.reserve(vitems.size());
+        for (int32_t i : vitems) links.push_back(c->h_vitem_link[(size_t)i]);      // (every chunk of a link: duplicates are dropped)
+        if (!value_union_build(boxes.data(), std::move(links), c->chunk_px, upx, uitems)) return fail(CELESTE_ERR_INVALID_ARG);
+    }
+    t->n_visits = (int64_t)visits.size(); t->n_vitems = (int64_t)vitems.size(); t->n_uitems = (int64_t)uitems.size();
     const int n_cand = n * c->M;                                 // candidate visits k = ti * M + j
     const int n_wblk = (n_cand + WORK_NT - 1) / WORK_NT;
     const size_t n_blk = (size_t)n_wblk * (WORK_CLASSES + 1);
@@ -1179,10 +1198,14 @@ static int targets_build(celeste_ctx_t *c, const std::vector<int32_t> &tg, celes
     LIST_ALLOC(t->d_needed, (size_t)c->S * sizeof(int32_t));
     LIST_ALLOC(t->d_visits, std::max<size_t>(visits.size(), 1) * sizeof(int32_t));
     LIST_ALLOC(t->d_vitems, std::max<size_t>(vitems.size(), 1) * sizeof(int32_t));
+    LIST_ALLOC(t->d_uitems, std::max<size_t>(uitems.size(), 1) * sizeof(int4));
+    LIST_ALLOC(t->d_upx, std::max<size_t>(upx.size(), 1) * sizeof(int32_t));
     LIST_ALLOC(d_blk, n_blk * sizeof(int32_t));
     LIST_TRY(hipMemcpy(t->d_targets, tg.data(), (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice));
     if (!visits.empty()) LIST_TRY(hipMemcpy(t->d_visits, visits.data(), visits.size() * sizeof(int32_t), hipMemcpyHostToDevice));
     if (!vitems.empty()) LIST_TRY(hipMemcpy(t->d_vitems, vitems.data(), vitems.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+    if (!uitems.empty()) LIST_TRY(hipMemcpy(t->d_uitems, uitems.data(), uitems.size() * sizeof(int4), hipMemcpyHostToDevice));
+    if (!upx.empty()) LIST_TRY(hipMemcpy(t->d_upx, upx.data(), upx.size() * sizeof(int32_t), hipMemcpyHostToDevice));
     LIST_TRY(hipMemset(t->d_needed, 0, (size_t)c->S * sizeof(int32_t)));
     // the half of setup_thread that depends on the targets alone (vp == nullptr: no SrcGeo): visit items and target marks
     const size_t setup_threads = (size_t)n * (c->dense ? 1 : c->M);
@@ -1270,7 +1293,20 @@ static int launch_prepared(celeste_ctx_t *c, const celeste_targets_t *t, const d
     hipLaunchKernelGGL(geo_prep_kernel, dim3(geo_blocks + (unsigned)t->n_visits), dim3(64), 0, stream, d_vp, c->d_images,
                        c->d_patches, c->d_vis_src, c->d_vis_img, c->K, c->d_srcimg, c->d_comps, t->d_visits, (int)geo_blocks,
                        c->S, c->d_geo);
-    if (t->n_vitems > 0) {
+    // the neighbours' light: every pixel the list wants once (value_union_kernel over the list's own items);
+    // CELESTE_NO_VALUE_UNION=1 (the A/B switch, read per call): once per link, the context's items of the list's targets
+    const char *no_union = getenv("CELESTE_NO_VALUE_UNION");
+    if (!(no_union && atoi(no_union) != 0)) {
+        if (t->n_uitems > 0) {
+            const bool wide_items = n_targets <= VALUE_WIDE_MAX && c->chunk_px == 256 && !getenv("CELESTE_NO_WIDE_VALUE");
+#define LAUNCH_UNION(WAVES)                                                                                                 \
+            hipLaunchKernelGGL((value_union_kernel<WAVES>), dim3((unsigned)t->n_uitems), dim3(64 * WAVES), 0, stream,       \
+                               c->d_patches, c->d_coefs, c->d_srcimg, c->d_comps, c->d_val_off, t->d_uitems, t->d_upx,      \
+                               c->NC, c->d_val)
+            if (wide_items) LAUNCH_UNION(4); else LAUNCH_UNION(1);
+#undef LAUNCH_UNION
+        }
+    } else if (t->n_vitems > 0) {
         const bool wide_items = n_targets <= VALUE_WIDE_MAX && c->chunk_px == 256 && !getenv("CELESTE_NO_WIDE_VALUE");
 #define LAUNCH_VALUE(WAVES)                                                                                                 \
         hipLaunchKernelGGL((value_kernel<double, WAVES>), dim3((unsigned)t->n_vitems), dim3(64 * WAVES), 0, stream,        \

@@ -967,9 +967,35 @@ setup_worklist_kernel(const double *__restrict__ vp, int S, SrcGeo *__restrict__
     }
 }
 
+// the light of one neighbour on the pixel (h0, w0) (0-based image coordinates) of its patch, into the neighbour's own patch
+// buffer `out`: the per-pixel body of value_kernel, whichever way the pixels are enumerated (an overlap rectangle:
+// value_pixels; a prepared list's offsets: value_union_kernel).  sh0, sw0 = 26 - si.m1, 26 - si.m2.  COH: the values are
+// for workgroups of the same launch (write-through stores).
+template <bool COH, typename R = double>
+__device__ __forceinline__ void value_pixel(const DevPatch &P, const SrcImg &si, const Comp *__restrict__ tc, int NC,
+                                            const double *__restrict__ coef, const double *__restrict__ etab, double sh0,
+                                            double sw0, int h0, int w0, double2 *__restrict__ out,
+                                            const float *__restrict__ tcf = nullptr) {
+    const double hh = (double)(h0 + 1), ww = (double)(w0 + 1);
+    double f0, f1;
+    if constexpr (sizeof(R) == 8) {
+        f0 = star_value(coef, hh + sh0, ww + sw0);
+        f1 = galaxy_value(tc, NC, hh - si.m1, ww - si.m2, etab);
+    } else {
+        // the two densities in single precision (differences of coordinates formed in double), the moments in double
+        f0 = (double)star_value_f(coef, (float)(hh + sh0), (float)(ww + sw0));
+        f1 = (double)galaxy_value_f(tcf, NC, (float)(hh - si.m1), (float)(ww - si.m2));
+    }
+    const double En = si.c0 * f0 + si.c1 * f1;                      // E_G_s.v  (elbo_objective.jl:62-65)
+    const double E2n = si.q0 * (f0 * f0) + si.q1 * (f1 * f1);
+    double2 *const o = out + ((h0 - P.off_h) + (int64_t)P.H2 * (w0 - P.off_w));
+    const double var = E2n - En * En;                               // var_G_s.v (:204)
+    if constexpr (COH) { stc<true>(&o->x, En); stc<true>(&o->y, var); }
+    else *o = make_double2(En, var);
+}
+
 // the light of one neighbour on pixels [p0, p1) of an overlap rectangle (h fastest, RH rows, corner (h_lo, w_lo) in 0-based
-// image coordinates), into the neighbour's own patch buffer `out`: value_kernel's loop, one wavefront.  COH: the values
-// are for workgroups of the same launch (write-through stores).
+// image coordinates), into the neighbour's own patch buffer `out`: value_kernel's loop, one wavefront.
 template <bool COH, typename R = double>
 __device__ __forceinline__ void value_pixels(int lane, const DevPatch &P, const SrcImg &si, const Comp *__restrict__ tc, int NC,
                                              const double *__restrict__ coefs, const double *__restrict__ etab, int h_lo,
@@ -981,23 +1007,7 @@ __device__ __forceinline__ void value_pixels(int lane, const DevPatch &P, const 
     for (int idx = p0 + lane; idx < p1; idx += 64) {
         int rw, rh;
         divmod_small(idx, RH, rRH, rw, rh);
-        const int h0 = h_lo + rh, w0 = w_lo + rw;  // 0-based image coordinates
-        const double hh = (double)(h0 + 1), ww = (double)(w0 + 1);
-        double f0, f1;
-        if constexpr (sizeof(R) == 8) {
-            f0 = star_value(coef, hh + sh0, ww + sw0);
-            f1 = galaxy_value(tc, NC, hh - si.m1, ww - si.m2, etab);
-        } else {
-            // the two densities in single precision (differences of coordinates formed in double), the moments in double
-            f0 = (double)star_value_f(coef, (float)(hh + sh0), (float)(ww + sw0));
-            f1 = (double)galaxy_value_f(tcf, NC, (float)(hh - si.m1), (float)(ww - si.m2));
-        }
-        const double En = si.c0 * f0 + si.c1 * f1;                      // E_G_s.v  (elbo_objective.jl:62-65)
-        const double E2n = si.q0 * (f0 * f0) + si.q1 * (f1 * f1);
-        double2 *const o = out + ((h0 - P.off_h) + (int64_t)P.H2 * (w0 - P.off_w));
-        const double var = E2n - En * En;                               // var_G_s.v (:204)
-        if constexpr (COH) { stc<true>(&o->x, En); stc<true>(&o->y, var); }
-        else *o = make_double2(En, var);
+        value_pixel<COH, R>(P, si, tc, NC, coef, etab, sh0, sw0, h_lo + rh, w_lo + rw, out, tcf);   // 0-based image coordinates
     }
 }
 
@@ -1173,6 +1183,68 @@ value_kernel(const DevPatch *__restrict__ patches, const double *__restrict__ co
     }
 #endif
 #undef VT
+}
+
+// value_kernel over a prepared list's pixel set (csrc/value_union.h): an item is {visit of the neighbour, first, count} and
+// renders pixels px_off[first, first + count) of that visit's patch -- offsets (h0 - off_h) + H2 (w0 - off_w) into the
+// neighbour's own buffer, ascending; each pixel the list wants once, however many of its targets want it.  Double precision
+// only (prepared lists do not serve fp32).  The staging and the per-pixel code (value_pixel) are value_kernel's: every pixel
+// gets the value value_kernel gives it.  A lane loads the offsets of its four trips of a 256-pixel block before the first
+// evaluation, so that no index load sits in front of a trip.  WAVES = 4: as value_kernel, an item's four trips on four
+// wavefronts (items of at most 256 pixels).
+template <int WAVES = 1>
+__global__ void __launch_bounds__(64 * WAVES)
+value_union_kernel(const DevPatch *__restrict__ patches, const double *__restrict__ coefs,
+                   const SrcImg *__restrict__ srcimg, const Comp *__restrict__ comps, const int64_t *__restrict__ val_off,
+                   const int4 *__restrict__ items, const int32_t *__restrict__ px_off, int NC, double2 *__restrict__ val) {
+    __shared__ double etab[64];
+    const int4 it = items[blockIdx.x];
+    const int sn = it.x, count = it.z;
+    const int32_t *__restrict__ po = px_off + it.y;
+    const int lane = threadIdx.x & 63;
+    int o0 = 0, o1 = 0, o2 = 0, o3 = 0;
+    if constexpr (WAVES == 1) {
+        if (lane < count) o0 = po[lane];
+        if (lane + 64 < count) o1 = po[lane + 64];
+        if (lane + 128 < count) o2 = po[lane + 128];
+        if (lane + 192 < count) o3 = po[lane + 192];
+    } else if ((int)threadIdx.x < count) o0 = po[threadIdx.x];
+    const DevPatch &P = patches[sn];
+    exp_table_init(etab);
+    const SrcImg si = srcimg[sn];
+    __shared__ Comp tc[14 * CEL_MAXK];
+    {
+        const double *src = reinterpret_cast<const double *>(comps + (size_t)sn * NC);
+        double *dst = reinterpret_cast<double *>(tc);
+        for (int i = threadIdx.x; i < NC * 8; i += 64 * WAVES) dst[i] = src[i];
+        __syncthreads();
+    }
+    const double *__restrict__ coef = coefs + (size_t)(CELESTE_MUTANT == 3 ? 0 : P.stamp) * (CEL_COEF * CEL_COEF);
+    const double sh0 = 26.0 - si.m1, sw0 = 26.0 - si.m2;
+    const int H2 = P.H2;
+    const float rH2 = 1.0f / (float)H2;
+    double2 *__restrict__ out = val + val_off[sn];
+    if constexpr (WAVES == 1) {
+        for (int base = 0;;) {
+            const int n = min(count - base, 256);
+            for (int p = lane; p < n; p += 64) {
+                int cw, ch;
+                divmod_small(o0, H2, rH2, cw, ch);
+                o0 = o1; o1 = o2; o2 = o3;
+                value_pixel<false, double>(P, si, tc, NC, coef, etab, sh0, sw0, P.off_h + ch, P.off_w + cw, out);
+            }
+            // (items of more than 256 pixels: a context made with a larger CELESTE_CHUNK_PX)
+            base += 256;
+            if (base >= count) break;
+            const int i = base + lane;
+            o0 = i < count ? po[i] : 0; o1 = i + 64 < count ? po[i + 64] : 0;
+            o2 = i + 128 < count ? po[i + 128] : 0; o3 = i + 192 < count ? po[i + 192] : 0;
+        }
+    } else if ((int)threadIdx.x < count) {
+        int cw, ch;
+        divmod_small(o0, H2, rH2, cw, ch);
+        value_pixel<false, double>(P, si, tc, NC, coef, etab, sh0, sw0, P.off_h + ch, P.off_w + cw, out);
+    }
 }
 
 // ---------------------------------------------------------------------------------------------

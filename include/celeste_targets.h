@@ -13,7 +13,11 @@
  * still alive, after which their handles are dangling.
  * Lists are made for the context's 256-pixel fp64 chunks: a call with CELESTE_FLAG_FP32 or CELESTE_FLAG_SPLIT, and a
  * Hessian batch small enough for the one-launch evaluation (<= 32 targets), runs celeste_elbo_eval_batch_device on the
- * list's targets instead -- same results, nothing saved.  CELESTE_NO_PREPARED=1 in the environment does so for every call. */
+ * list's targets instead -- same results, nothing saved.  CELESTE_NO_PREPARED=1 in the environment does so for every call.
+ * A list also holds the set of neighbour pixels its targets gather, each once (4 bytes per pixel of device memory: 8 MB for
+ * 2000 targets of a single field, 138 MB for 30 000 targets of a 4 x 4 grid of fields; CELESTE_ERR_ALLOC if it does not
+ * fit), so that a sweep renders a neighbour wanted by several targets once; CELESTE_NO_VALUE_UNION=1 in the environment
+ * renders it once per target as celeste_elbo_eval_batch_device does -- same results. */
 typedef struct celeste_targets celeste_targets_t;
 int celeste_targets_create(celeste_ctx_t *ctx, int32_t n_targets, const int32_t *targets, celeste_targets_t **out);
 int celeste_targets_create_device(celeste_ctx_t *ctx, int32_t n_targets, const int32_t *d_targets, void *stream,
