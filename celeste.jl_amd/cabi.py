@@ -492,6 +492,9 @@ def problem_from_table(images, table, neighbors: Optional[Sequence[Sequence[int]
             stamps.append(st.reshape(-1))
         return stamp_key[key]
     from .model import ConstantPSFMap
+    # a table built on the device (prep.patch_table) brings the stamps of its eigen-PSF images: table.stamps[table.stamp[e]]
+    dev_stamp, dev_stamps = getattr(table, "stamp", None), getattr(table, "stamps", None)
+    from_device = []
     for n, im in enumerate(images):
         e = np.flatnonzero(table.image == n)
         J = np.asarray(im.wcs_jacobian, dtype=np.float64)
@@ -502,6 +505,8 @@ def problem_from_table(images, table, neighbors: Optional[Sequence[Sequence[int]
         arr["psf"][e] = psf.ctypes.data
         if isinstance(im.psfmap, ConstantPSFMap):
             arr["stamp"][e] = stamp_index(im.psfmap.stamp)
+        elif dev_stamp is not None and dev_stamps is not None and e.size and (dev_stamp[e] >= 0).all():
+            from_device.append(e)
         else:
             for k in e.tolist():
                 arr["stamp"][k] = stamp_index(im.psfmap(table.pixel_center[k, 0], table.pixel_center[k, 1]))
@@ -513,7 +518,17 @@ def problem_from_table(images, table, neighbors: Optional[Sequence[Sequence[int]
         pb.patch_image = np.ascontiguousarray(table.image, dtype=np.int32)
     else:
         assert E == S * N
-    pb.stamps = np.ascontiguousarray(np.stack(stamps))
+    if from_device:
+        # the two stamp tables, one after the other: this function's (constant maps), then the device's
+        for e in from_device:
+            arr["stamp"][e] = len(stamps) + dev_stamp[e]
+        dev_stamps = np.ascontiguousarray(dev_stamps, dtype=np.float64).reshape(-1, STAMP * STAMP)
+        pb.stamps = np.concatenate([np.stack(stamps), dev_stamps]) if stamps else dev_stamps
+        n_stamps = len(stamps) + len(dev_stamps)
+        pb._keep.append(table)     # (dev_stamps may be a view of memory the table owns)
+    else:
+        pb.stamps = np.ascontiguousarray(np.stack(stamps))
+        n_stamps = len(stamps)
     if neighbors is None:
         neighbors = [[] for _ in range(S)]
     off = np.zeros(S + 1, dtype=np.int64)
@@ -525,7 +540,7 @@ def problem_from_table(images, table, neighbors: Optional[Sequence[Sequence[int]
     pb.neighbors = [list(r) for r in neighbors]
     pb.c_prior = prior_struct(prior) if prior is not None else None
     pb.c = ProblemT()
-    pb.c.n_images, pb.c.n_sources, pb.c.psf_K, pb.c.n_stamps = N, S, psf_K, len(stamps)
+    pb.c.n_images, pb.c.n_sources, pb.c.psf_K, pb.c.n_stamps = N, S, psf_K, n_stamps
     if pb.c_images is not None:
         pb.c.images = pb.c_images
     pb.c.patches = pb.c_patches

@@ -69,16 +69,19 @@ class FieldContext:
 
     @classmethod
     def from_catalog(cls, images, catalog, psf_K: int = 2, prior: Optional[dict] = None, device: int = 0,
-                     image_set: Optional["cabi.ImageSet"] = None, sparse: Optional[bool] = None):
+                     image_set: Optional["cabi.ImageSet"] = None, sparse: Optional[bool] = None,
+                     prep_device: Optional[int] = None, prep_images=None):
         """The context of ParallelRun's box inference for a catalog: get_sky_patches + find_neighbors
         (imaged_sources.jl:165-182, 232-244) through model.patch_table -- the same patches and neighbour lists as
         FieldContext(images, get_sky_patches(images, catalog), neighbor_map(patches)), an order of magnitude less host
         time (no per-patch objects).  sparse (default: when there are more than 8 images) selects the sparse patch
-        list.  The table stays available as `ctx.table` (costs(), neighbors)."""
+        list.  The table stays available as `ctx.table` (costs(), neighbors).
+        prep_device (a HIP ordinal) or prep_images (a prep.PrepImages over `images`): the table, the neighbour lists and
+        the stamps of eigen-PSF images are built on the device (prep.patch_table) instead of on the host."""
         from . import model
         if sparse is None:
             sparse = len(images) > 8
-        table = model.patch_table(images, catalog, sparse=sparse)
+        table = model.table_for(images, catalog, sparse, prep_device, prep_images)
         neighbors = table.neighbors()
         problem = cabi.problem_from_table(images, table, neighbors, psf_K=psf_K, prior=prior,
                                           marshal_images=image_set is None)

@@ -76,11 +76,12 @@ class FieldGroup:
 
     @classmethod
     def from_catalog(cls, images, catalog, psf_K: int = 2, prior: Optional[dict] = None, devices: Sequence[int] = (0,),
-                     sparse: Optional[bool] = None):
+                     sparse: Optional[bool] = None, prep_device: Optional[int] = None, prep_images=None):
+        """prep_device / prep_images: as FieldContext.from_catalog (the table is built on one device, for every member)"""
         from . import model
         if sparse is None:
             sparse = len(images) > 8
-        table = model.patch_table(images, catalog, sparse=sparse)
+        table = model.table_for(images, catalog, sparse, prep_device, prep_images)
         neighbors = table.neighbors()
         problem = cabi.problem_from_table(images, table, neighbors, psf_K=psf_K, prior=prior)
         g = cls(images, None, neighbors, psf_K=psf_K, prior=prior, devices=devices, problem=problem)

@@ -297,7 +297,7 @@ def group_joint_infer(group, catalog, target_sources: Sequence[int], neighbors: 
 def infer_box(images, box: BoundingBox, catalog=None, method: str = "joint_vi", cfg: Optional[ElboConfig] = None,
               n_iters: int = NUM_JOINT_VI_ITERS, device: int = 0, schedule: str = "cyclades",
               devices: Optional[Sequence[int]] = None, match_radius: float = 1.0 / 3600.0,
-              mcmc_config=None) -> list:
+              mcmc_config=None, prep: str = "host") -> list:
     """infer_box / _infer_box (ParallelRun.jl:610-672): targets = catalog entries strictly inside the box, neighbours
     may lie outside it, then joint or single variational inference on the device (method in {joint_vi, single_vi}:
     one OptimizedSource per target) or MCMC (method = "mcmc": process_source_mcmc, ParallelRun.jl:504-543, with
@@ -306,7 +306,12 @@ def infer_box(images, box: BoundingBox, catalog=None, method: str = "joint_vi", 
     patches for every catalog entry (get_sky_patches).  match_radius: the world distance under which detections of
     different images are one object (detection.jl's 1 arcsec; used only without a catalog).
     devices: HIP ordinals of a device group (celeste_group_*: one process, the reference's N workers = N devices, RCCL
-    inside the library); None = the one `device`."""
+    inside the library); None = the one `device`.
+    prep: "host" builds the patch table, the neighbour lists, the stamps of a variable PSF and the sky flags of a catalog on
+    the host (model.patch_table, infer.bad_sky_flags); "device" builds them on the device (prep.patch_table,
+    prep.bad_sky_flags: one upload of the planes serves both).  Detection (catalog=None) brings its own patches either way."""
+    if prep not in ("host", "device"):
+        raise ValueError("prep must be 'host' or 'device', not %r" % (prep,))
     if method == "mcmc" and devices is not None:
         raise ValueError("method='mcmc' runs on one device: pass device=..., not devices=... (device groups run VI only)")
     if catalog is None:
@@ -314,11 +319,26 @@ def infer_box(images, box: BoundingBox, catalog=None, method: str = "joint_vi", 
     targets = [i for i, ce in enumerate(catalog) if box.contains(ce.pos)]
     if not targets:
         return []
+    if prep == "device":
+        from .prep import PrepImages
+        with PrepImages(images, devices[0] if devices is not None else device) as pi:
+            return _infer_box_catalog(images, catalog, targets, method, cfg, n_iters, device, schedule, devices, mcmc_config, pi)
+    return _infer_box_catalog(images, catalog, targets, method, cfg, n_iters, device, schedule, devices, mcmc_config, None)
+
+
+def _infer_box_catalog(images, catalog, targets, method, cfg, n_iters, device, schedule, devices, mcmc_config, pi) -> list:
+    """infer_box with a catalog.  pi: a prep.PrepImages over `images` (the table, neighbour lists, stamps and sky flags come
+    from the device) or None (from the host)."""
+    def sky_flags(dev):
+        if pi is not None:
+            from . import prep
+            return prep.bad_sky_flags([catalog[t] for t in targets], images, prep_images=pi)
+        return bad_sky_flags([catalog[t] for t in targets], images, dev)
     if method == "mcmc":
         # the MCMC library's own context over the problem of FieldContext.from_catalog (no VI context is created)
         from . import cabi, model
         from .mcmc import MCMCContext, run_ais_batch
-        table = model.patch_table(images, catalog, sparse=len(images) > 5)
+        table = model.table_for(images, catalog, len(images) > 5, prep_images=pi)
         mc = MCMCContext(cabi.problem_from_table(images, table, table.neighbors()), device)
         try:
             return run_ais_batch(mc, catalog, targets, mcmc_config)
@@ -328,7 +348,7 @@ def infer_box(images, box: BoundingBox, catalog=None, method: str = "joint_vi", 
         from .group import FieldGroup
         if schedule != "cyclades":
             raise ValueError("a device group runs the reference's Cyclades schedule")
-        group = FieldGroup.from_catalog(images, catalog, devices=list(devices), sparse=len(images) > 5)
+        group = FieldGroup.from_catalog(images, catalog, devices=list(devices), sparse=len(images) > 5, prep_images=pi)
         failed = set()
         try:
             if method == "joint_vi":
@@ -339,12 +359,12 @@ def infer_box(images, box: BoundingBox, catalog=None, method: str = "joint_vi", 
                 raise ValueError("unknown method: %s" % method)
         finally:
             group.close()
-        flags = bad_sky_flags([catalog[t] for t in targets], images, devices[0])
+        flags = sky_flags(devices[0])
         return [OptimizedSource(float(catalog[t].pos[0]), float(catalog[t].pos[1]), vs[k].copy(), flags[k], t in failed)
                 for k, t in enumerate(targets)]
     # patches and neighbour lists as arrays (model.patch_table: the geometry of get_sky_patches / find_neighbors
     # without a Python object per patch); several fields: sources see a few images each -> sparse patch list
-    ctx = FieldContext.from_catalog(images, catalog, device=device, sparse=len(images) > 5)
+    ctx = FieldContext.from_catalog(images, catalog, device=device, sparse=len(images) > 5, prep_images=pi)
     neighbors = ctx.problem.neighbors
     failed: set = set()
     try:
@@ -357,7 +377,7 @@ def infer_box(images, box: BoundingBox, catalog=None, method: str = "joint_vi", 
             raise ValueError("unknown method: %s" % method)
     finally:
         ctx.close()
-    flags = bad_sky_flags([catalog[t] for t in targets], images, device)
+    flags = sky_flags(device)
     return [OptimizedSource(float(catalog[t].pos[0]), float(catalog[t].pos[1]), vs[k].copy(), flags[k], t in failed)
             for k, t in enumerate(targets)]
 

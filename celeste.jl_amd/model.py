@@ -357,7 +357,10 @@ class PatchTable:
 
     def neighbors(self) -> List[List[int]]:
         """find_neighbors for every source (imaged_sources.jl:232-244): sources whose boxes overlap in some image;
-        ascending, empty boxes overlap nothing"""
+        ascending, empty boxes overlap nothing.  A table built on the device (prep.patch_table) carries them already."""
+        lists = getattr(self, "neighbor_lists", None)
+        if lists is not None:
+            return lists
         ok = (self.H2 > 0) & (self.W2 > 0)
         pairs = []
         for n in range(self.n_images):
@@ -386,10 +389,14 @@ class PatchTable:
 
 
 def patch_table(images: Sequence[Image], catalog: Sequence[CatalogEntry], radius_override_pix: float = math.nan,
-                sparse: bool = False) -> PatchTable:
+                sparse: bool = False, device=None) -> PatchTable:
     """get_sky_patches (imaged_sources.jl:165-182) without the per-patch objects: the same boxes (box_from_catalog /
     box_around_point / clamp_box, called as the object path calls them), centres and active-pixel counts, as arrays.
-    sparse=True keeps only the pairs that cover a pixel, tried for the same sources as get_sky_patches(sparse=True)."""
+    sparse=True keeps only the pairs that cover a pixel, tried for the same sources as get_sky_patches(sparse=True).
+    device (a HIP ordinal; default None: this function, on the host): the table is built by prep.patch_table."""
+    if device is not None:
+        from . import prep
+        return prep.patch_table(images, catalog, radius_override_pix=radius_override_pix, sparse=sparse, device=device)
     S, N = len(catalog), len(images)
     src, img_i, boxes = [], [], []
     cache = {}
@@ -438,6 +445,15 @@ def patch_table(images: Sequence[Image], catalog: Sequence[CatalogEntry], radius
             c0, c1 = box[e, 2] - 1, np.maximum(box[e, 3], box[e, 2] - 1)
             active[e] = np.where((h2[e] > 0) & (w2[e] > 0), sat[r1, c1] - sat[r0, c1] - sat[r1, c0] + sat[r0, c0], 0)
     return PatchTable(S, N, not sparse, source, image, box, pixel_center, world_center, active)
+
+
+def table_for(images, catalog, sparse: bool, prep_device=None, prep_images=None) -> PatchTable:
+    """the patch table of a from_catalog constructor: patch_table on the host, or prep.patch_table when a device or a
+    prep.PrepImages is given"""
+    if prep_images is not None or prep_device is not None:
+        from . import prep
+        return prep.patch_table(images, catalog, sparse=sparse, device=prep_device or 0, prep_images=prep_images)
+    return patch_table(images, catalog, sparse=sparse)
 
 
 def find_neighbors(patches: List[List[ImagePatch]], target: int) -> List[int]:

@@ -1,0 +1,144 @@
+/* celeste_prep.h -- C ABI of libceleste_prep.so: the input preparation of a box on an AMD Instinct MI355X (gfx950).
+ *
+ * What model.patch_table, PatchTable.neighbors, SDSSPSFMap.__call__ and infer.bad_sky compute on the host, one (source,
+ * image) pair at a time, for a whole catalog in a fixed number of launches: the patch geometry of get_sky_patches
+ * (imaged_sources.jl:120-223), the neighbour lists of find_neighbors (imaged_sources.jl:232-244), the eigen-PSF stamps of
+ * SDSSIO.jl:239-299 and the sky check of ParallelRun.jl:437-460.  Only the affine WCS pix = J (world - world0) + pix0.
+ *
+ * All arithmetic is fp64 (the median: Float32, as the pixels are), compiled without contraction: a * b + c is a rounded
+ * product and a rounded sum everywhere in this library.  No result uses a floating-point atomic; results repeat bit for
+ * bit and do not depend on the launch geometry.
+ *
+ * Geometry of the pair (source s, image n), one thread per pair:
+ *     d = pos - world0;  pc1 = J11 d1 + J12 d2 + pix01;  pc2 = J21 d1 + J22 d2 + pix02       (Image.world_to_pix)
+ *     tried: always with CELESTE_PREP_FLAG_DENSE; otherwise when -reach < pc1 < H + 1 + reach and -reach < pc2 < W + 1 + reach,
+ *            reach = (radius_override_pix is NaN ? 25 : radius_override_pix) + 1
+ *     r = radius_override_pix unless it is NaN; then choose_patch_radius with width_scale 1.2, max_radius 25:
+ *         ow = (is_star ? 0 : 1.2 gal_radius_px / 0.67) + psf_width;   f = flux[band - 1];  not f > 0: INVALID_ARG
+ *         p90 = C1 / (C2 ow);  pt = p90 if p90 < eps / (20 f), else eps / (20 f)      C1 = exp(-0.5 * 1.64^2), C2 = sqrt(2 pi)
+ *         rhs = log(pt) + C3 + log(ow);  rq = sqrt(((-2) (ow ow)) rhs);  r = 25 if 25 < rq, else rq     C3 = 0.5 log(2 pi)
+ *         (C1, C2, C3 are evaluated once, by the host's libm, as Python's math module evaluates them; log and sqrt are the
+ *         device's: sqrt is correctly rounded, log may differ from libm in the last place.)  A NaN position, radius or
+ *         pixel coordinate of a tried pair: INVALID_ARG (the host raises there).
+ *     box: rows rint(pc1 - r) .. rint(pc1 + r), columns rint(pc2 - r) .. rint(pc2 + r), rint = ties to even;
+ *          clamp_box: first row into 1 .. H + 1, last row into 0 .. H, columns likewise with W.
+ *     pixel_center = ((first row + last row) / 2, (first column + last column) / 2)
+ *     world_center = J^-1 (pixel_center - pix0) + world0 by LU with partial pivoting (rows swapped when |J21| > |J11|):
+ *         l = J21 / J11;  u = J22 - l J12;  y2 = b2 - l b1;  x2 = y2 / u;  x1 = (b1 - J12 x2) / J11.
+ *     An entry is kept for every tried pair (DENSE) or for the tried pairs whose clamped box holds a pixel; entries are
+ *     ordered by (source, image) -- an exclusive scan over the pairs in that order, no atomics.
+ * active_pixels: the pixels of the box that are not NaN, one wavefront per entry (integer counts).
+ * Neighbours of s: the sources t != s with a non-empty box that overlaps one of s's non-empty boxes in the same image
+ *     (inclusive ranges: first <= other's last and other's first <= last, rows and columns); ascending, each once.
+ * Stamps (CELESTE_PREP_FLAG_STAMPS), one workgroup per entry of an image with an eigen-PSF, at (x, y) = pixel_center:
+ *     px_0 = 1, px_i = px_(i-1) (0.001 (x - 1));  py_j likewise with y;
+ *     w_k = sum over i ascending, inside it j ascending, of cmat[i][j][k] (px_i py_j)
+ *     stamps[stamp][p] = sum over k ascending of rrows[p][k] w_k,  p = 0 .. 51 * 51 - 1
+ *     -- the column-major raw stamp celeste_problem_t.stamps takes (p = row + 51 column).
+ * Sky check of a position, on the first image of band 4 (none: every flag 0, no launch), one workgroup per position:
+ *     h = rint(pc1) into 1 .. H, w = rint(pc2) into 1 .. W;  claimed = (double)sky[h, w] * (double)nelec_per_nmgy[h]
+ *     the box of radius 50 as above (at most 102 x 102 pixels);  its n pixels that are not NaN;  k = n / 2;
+ *     median = the k-th smallest (0-based) for odd n, (the (k-1)-th + the k-th) * 0.5f in Float32 for even n,
+ *     by an 8-bit radix select on ordered keys;  flag = n > 0 and claimed + 5 < (double)median.
+ *
+ * Thread safety: calls are serialised inside the library.  Without a HIP device the entry points that compute return
+ * CELESTE_PREP_ERR_NO_DEVICE -- there is no CPU path.  Invalid arguments are refused before any HIP call (the flux and NaN
+ * checks above are part of the geometry kernel and are reported when it has run). */
+#ifndef CELESTE_PREP_H
+#define CELESTE_PREP_H
+
+#include <stdint.h>
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+#define CELESTE_PREP_ABI_VERSION 100
+#define CELESTE_PREP_STAMP 51          /* rnrow = rncol of an eigen-PSF */
+#define CELESTE_PREP_MAX_POLY 8        /* ni, nj <= 8 */
+#define CELESTE_PREP_MAX_NK 16         /* nk <= 16 */
+#define CELESTE_PREP_N_STAGES 5        /* celeste_prep_last_ms */
+
+enum {
+    CELESTE_PREP_OK = 0,
+    CELESTE_PREP_ERR_INVALID_ARG = 1,
+    CELESTE_PREP_ERR_NO_DEVICE = 2,
+    CELESTE_PREP_ERR_HIP = 3,
+    CELESTE_PREP_ERR_ALLOC = 4
+};
+
+enum {
+    CELESTE_PREP_FLAG_DENSE = 1u,    /* an entry for every (source, image) pair, empty boxes included */
+    CELESTE_PREP_FLAG_STAMPS = 2u    /* evaluate the eigen-PSF stamps */
+};
+
+typedef struct celeste_prep_image_t {
+    int32_t H, W;
+    int32_t band;                    /* 1 .. 5 */
+    int32_t reserved;
+    const float *pixels;             /* pixel (h, w), 1-based, is pixels[(h - 1) stride_h + (w - 1) stride_w] */
+    int64_t stride_h, stride_w;      /* in elements: (W, 1), a row-major H x W array, or (1, H), a column-major plane */
+    const float *sky;                /* the sky plane, nmgy; read for the first image of band 4 only, may be NULL elsewhere */
+    int64_t sky_stride_h, sky_stride_w;
+    const float *nelec_per_nmgy;     /* H */
+    double wcs_jacobian[4];          /* J11, J21, J12, J22, as celeste_patch_t.wcs_jacobian */
+    double wcs_world0[2], wcs_pix0[2];
+    double psf_width;                /* get_psf_width(psf, 1.2) */
+    double epsilon;                  /* sky[H / 2, W / 2], 1-based */
+    int32_t rnrow, rncol;            /* eigen-PSF: both CELESTE_PREP_STAMP; ignored when rrows is NULL */
+    int32_t ni, nj, nk;
+    int32_t reserved2;
+    const double *rrows;             /* (rnrow rncol) x nk, row-major: rrows[p nk + k]; NULL: a constant PSF map */
+    const double *cmat;              /* ni x nj x nk, row-major: cmat[(i nj + j) nk + k] */
+} celeste_prep_image_t;
+
+typedef struct celeste_prep_source_t {
+    double pos[2];
+    int32_t is_star;
+    int32_t reserved;
+    double flux[5];                  /* the star's fluxes if is_star, else the galaxy's, nmgy */
+    double gal_radius_px;
+} celeste_prep_source_t;
+
+/* page-locked host arrays owned by the result; E = n_entries, S = n_sources */
+typedef struct celeste_prep_table_t {
+    int64_t n_entries, n_sources, n_neighbors, n_stamps;
+    const int32_t *source, *image;   /* [E], sorted by (source, image) */
+    const int64_t *box;              /* [E][4]: first row, last row, first column, last column; 1-based, inclusive, clamped */
+    const double *pixel_center;      /* [E][2] */
+    const double *world_center;      /* [E][2] */
+    const int64_t *active_pixels;    /* [E] */
+    const int64_t *nbr_offsets;      /* [S + 1] */
+    const int32_t *nbr_index;        /* [n_neighbors]: the neighbours of s are nbr_index[nbr_offsets[s] .. nbr_offsets[s + 1]) */
+    const int32_t *stamp;            /* [E]: index into stamps, -1 for an image with a constant map; NULL without FLAG_STAMPS */
+    const double *stamps;            /* [n_stamps][51 * 51], column-major raw stamps; NULL without FLAG_STAMPS */
+} celeste_prep_table_t;
+
+typedef struct celeste_prep_images celeste_prep_images_t;
+typedef struct celeste_prep_result celeste_prep_result_t;
+
+int celeste_prep_version(void);
+const char *celeste_prep_strerror(int status);
+
+/* Uploads the planes, calibrations and eigen-PSFs of n_images images to `device`; the host arrays are not needed after
+ * the call. */
+int celeste_prep_images_create(int device, int32_t n_images, const celeste_prep_image_t *images, celeste_prep_images_t **handle);
+void celeste_prep_images_destroy(celeste_prep_images_t *handle);
+
+/* The patch table, neighbour lists and (FLAG_STAMPS) stamps of n_sources sources on the images of `handle`. */
+int celeste_prep_patches(celeste_prep_images_t *handle, int64_t n_sources, const celeste_prep_source_t *sources,
+                         double radius_override_pix, uint32_t flags, celeste_prep_result_t **result);
+int celeste_prep_result_get(const celeste_prep_result_t *result, celeste_prep_table_t *table);
+void celeste_prep_result_destroy(celeste_prep_result_t *result);
+
+/* flags[i] = the sky check of pos[2 i], pos[2 i + 1], i < n */
+int celeste_prep_bad_sky(celeste_prep_images_t *handle, int64_t n, const double *pos, uint8_t *flags);
+
+/* device time of the stages of the last call of this process, in milliseconds: geometry and compaction, active pixels,
+ * neighbours, stamps (celeste_prep_patches; the sky check's slot is 0), sky check (celeste_prep_bad_sky; the others 0) */
+int celeste_prep_last_ms(float ms[CELESTE_PREP_N_STAGES]);
+
+#ifdef __cplusplus
+}
+#endif
+#endif /* CELESTE_PREP_H */
