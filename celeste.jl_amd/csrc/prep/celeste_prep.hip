@@ -10,6 +10,8 @@
 //                            per source: where its links start; its sorted links without repeats (count, then fill)
 //   prep_stamp_kernel        one workgroup per entry: polynomial weights, then the weighted sum of eigen-images
 //   prep_sky_kernel          one workgroup per position: the median of its box by radix select, the flag
+// and for detections (prep_detected.h): prep_det_world_kernel, prep_match_kernel, prep_append_kernel,
+//   prep_object_ranges_kernel, prep_entry_kernel, prep_detected_geometry_kernel -- then the stages above from the compaction on
 // Scans and sorts are hipCUB's (integer keys: a stable radix sort, results do not depend on the launch geometry).
 // The file is compiled with -ffp-contract=off.
 #include <hip/hip_runtime.h>
@@ -51,6 +53,21 @@ __device__ __forceinline__ void world_to_pix(const PrepImg &im, double x, double
     const double d1 = x - im.w0[0], d2 = y - im.w0[1];
     pc1 = (im.J11 * d1 + im.J12 * d2) + im.p0[0];
     pc2 = (im.J21 * d1 + im.J22 * d2) + im.p0[1];
+}
+
+// J x = (c1, c2) - pix0 by LU with partial pivoting; (w1, w2) = x + world0
+__device__ __forceinline__ void pix_to_world(const PrepImg &im, double c1, double c2, double &w1, double &w2) {
+    double a11 = im.J11, a12 = im.J12, a21 = im.J21, a22 = im.J22, b1 = c1 - im.p0[0], b2 = c2 - im.p0[1];
+    if (fabs(a21) > fabs(a11)) {
+        double t = a11; a11 = a21; a21 = t;
+        t = a12; a12 = a22; a22 = t;
+        t = b1; b1 = b2; b2 = t;
+    }
+    const double l = a21 / a11;
+    const double u = a22 - l * a12;
+    const double x2 = (b2 - l * b1) / u;
+    const double x1 = (b1 - a12 * x2) / a11;
+    w1 = x1 + im.w0[0]; w2 = x2 + im.w0[1];
 }
 
 // the clamped box of radius r around (pc1, pc2): first row, last row, first column, last column
@@ -119,18 +136,7 @@ __global__ void __launch_bounds__(PREP_BLOCK) prep_compact_kernel(const PrepImg 
     E.ebox[e] = b;
     const double c1 = (double)(b.x + b.y) / 2.0, c2 = (double)(b.z + b.w) / 2.0;
     E.pc[2 * (int64_t)e] = c1; E.pc[2 * (int64_t)e + 1] = c2;
-    // J x = pixel_center - pix0 by LU with partial pivoting
-    double a11 = im.J11, a12 = im.J12, a21 = im.J21, a22 = im.J22, b1 = c1 - im.p0[0], b2 = c2 - im.p0[1];
-    if (fabs(a21) > fabs(a11)) {
-        double t = a11; a11 = a21; a21 = t;
-        t = a12; a12 = a22; a22 = t;
-        t = b1; b1 = b2; b2 = t;
-    }
-    const double l = a21 / a11;
-    const double u = a22 - l * a12;
-    const double x2 = (b2 - l * b1) / u;
-    const double x1 = (b1 - a12 * x2) / a11;
-    E.wc[2 * (int64_t)e] = x1 + im.w0[0]; E.wc[2 * (int64_t)e + 1] = x2 + im.w0[1];
+    pix_to_world(im, c1, c2, E.wc[2 * (int64_t)e], E.wc[2 * (int64_t)e + 1]);
     const bool nonempty = b.y >= b.x && b.w >= b.z;
     E.key[e] = nonempty ? (((unsigned long long)n << 32) | (unsigned long long)(uint32_t)b.x) : ((unsigned long long)N << 32);
     E.val[e] = e;
@@ -356,6 +362,7 @@ __global__ void __launch_bounds__(PREP_BLOCK) prep_sky_kernel(const PrepImg *img
 
 static std::mutex g_mu;                 // one call at a time
 static float g_last_ms[CELESTE_PREP_N_STAGES] = {0, 0, 0, 0, 0};
+static float g_det_ms[CELESTE_PREP_DETECTED_N_STAGES] = {0, 0, 0, 0, 0, 0};   // of the last call, when it was celeste_prep_detected
 
 // One stream per device, made on first use and kept for the life of the process (calls are serialised by g_mu): the HIP
 // runtime has been seen writing into a stream object after hipStreamDestroy freed it (profiles/r08_stale_stream_write.md),
@@ -380,6 +387,8 @@ struct celeste_prep_result {
     void *block = nullptr;              // page-locked
     size_t bytes = 0;
     celeste_prep_table_t table;
+    bool has_catalog = false;
+    celeste_prep_catalog_t catalog;
 };
 
 static int prep_stream(int device, hipStream_t *out) {
@@ -397,15 +406,23 @@ struct PrepCall {
     std::vector<void *> bufs;
     hipStream_t stream = nullptr;
     hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    hipEvent_t dev[3] = {nullptr, nullptr, nullptr};     // celeste_prep_detected's own stages
     ~PrepCall() {
         if (stream) (void)hipStreamSynchronize(stream);
         for (auto e : ev) if (e) (void)hipEventDestroy(e);
+        for (auto e : dev) if (e) (void)hipEventDestroy(e);
         for (void *p : bufs) (void)hipFree(p);
     }
     int open(int device) {
         int st = prep_stream(device, &stream);
         if (st) { stream = nullptr; return st; }
         for (auto &e : ev) PREP_HIP(hipEventCreate(&e));
+        return CELESTE_PREP_OK;
+    }
+    int open_detected(int device) {
+        int st = open(device);
+        if (st) return st;
+        for (auto &e : dev) PREP_HIP(hipEventCreate(&e));
         return CELESTE_PREP_OK;
     }
     template <class T> int alloc(T **dst, size_t n) {
@@ -583,6 +600,24 @@ static size_t carve(size_t *at, size_t bytes) {
     return o;
 }
 
+// what a geometry kernel leaves for the P pairs; err[0]: an invalid pair was met, err[1]: the largest number of rows of a box
+struct PrepPairs {
+    int32_t *keep = nullptr, *off = nullptr, *err = nullptr;
+    int4 *pbox = nullptr;
+    int alloc(PrepCall &call, int64_t P) {
+        int st;
+        if ((st = call.alloc(&keep, (size_t)P)) || (st = call.alloc(&off, (size_t)P)) || (st = call.alloc(&pbox, (size_t)P)) ||
+            (st = call.alloc(&err, 2)))
+            return st;
+        return CELESTE_PREP_OK;
+    }
+};
+
+struct PrepExtra { const void *dptr; size_t bytes; size_t at; const char *host; };
+
+static int prep_table_stages(celeste_prep_images_t *handle, PrepCall &call, int64_t S, int64_t P, const PrepPairs &G, int max_rows,
+                             bool want_stamps, PrepExtra *extra, int n_extra, celeste_prep_result_t **result);
+
 extern "C" int celeste_prep_patches(celeste_prep_images_t *handle, int64_t n_sources, const celeste_prep_source_t *sources,
                                     double radius_override_pix, uint32_t flags, celeste_prep_result_t **result) {
     // ---- arguments
@@ -610,32 +645,47 @@ extern "C" int celeste_prep_patches(celeste_prep_images_t *handle, int64_t n_sou
     if (st) return st;
     hipStream_t q = call.stream;
     for (float &m : g_last_ms) m = 0.0f;
+    for (float &m : g_det_ms) m = 0.0f;
 
-    // ---- geometry, compaction
-    celeste_prep_source_t *d_src; int32_t *d_keep, *d_off, *d_err; int4 *d_pbox;
-    if ((st = call.alloc(&d_src, (size_t)S)) || (st = call.alloc(&d_keep, (size_t)P)) || (st = call.alloc(&d_off, (size_t)P)) ||
-        (st = call.alloc(&d_pbox, (size_t)P)) || (st = call.alloc(&d_err, 1)))
-        return st;
-    int64_t E = 0;
+    // ---- geometry
+    PrepPairs G;
+    celeste_prep_source_t *d_src;
+    if ((st = call.alloc(&d_src, (size_t)S)) || (st = G.alloc(call, P))) return st;
     PREP_HIP(hipEventRecord(call.ev[0], q));
     if (P > 0) {
         PREP_HIP(hipMemcpyAsync(d_src, sources, (size_t)S * sizeof(celeste_prep_source_t), hipMemcpyHostToDevice, q));
-        PREP_HIP(hipMemsetAsync(d_err, 0, sizeof(int32_t), q));
+        PREP_HIP(hipMemsetAsync(G.err, 0, 2 * sizeof(int32_t), q));
         hipLaunchKernelGGL(prep_geometry_kernel, dim3(blocks_for(P)), dim3(PREP_BLOCK), 0, q, handle->d_imgs, N, d_src, P,
-                           has_override ? radius_override_pix : (double)NAN, reach, dense ? 1 : 0, C, d_keep, d_pbox, d_err);
+                           has_override ? radius_override_pix : (double)NAN, reach, dense ? 1 : 0, C, G.keep, G.pbox, G.err);
         PREP_HIP(hipGetLastError());
+    }
+    return prep_table_stages(handle, call, S, P, G, max_rows, want_stamps, nullptr, 0, result);
+}
+
+// The stages behind the geometry kernel, which has filled G for the P = S N pairs (call.ev[0] lies in front of it): compaction,
+// active pixels, neighbours, stamps, and the table in one page-locked block.  max_rows: no box has more rows; < 0: the largest
+// number of rows is read from G.err[1].  extra: n_extra device arrays that go into the same block (a catalog's).
+static int prep_table_stages(celeste_prep_images_t *handle, PrepCall &call, int64_t S, int64_t P, const PrepPairs &G, int max_rows,
+                             bool want_stamps, PrepExtra *extra, int n_extra, celeste_prep_result_t **result) {
+    const int N = handle->n_images;
+    hipStream_t q = call.stream;
+    int st;
+    int32_t *d_keep = G.keep, *d_off = G.off, *d_err = G.err; int4 *d_pbox = G.pbox;
+    int64_t E = 0;
+    if (P > 0) {
         size_t tb = 0;
         PREP_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, d_keep, d_off, (int)P, q));
         char *d_tmp;
         if ((st = call.alloc(&d_tmp, tb))) return st;
         PREP_HIP(hipcub::DeviceScan::ExclusiveSum(d_tmp, tb, d_keep, d_off, (int)P, q));
-        int32_t last[3] = {0, 0, 0};
+        int32_t last[4] = {0, 0, 0, 0};
         PREP_HIP(hipMemcpyAsync(&last[0], d_off + (P - 1), sizeof(int32_t), hipMemcpyDeviceToHost, q));
         PREP_HIP(hipMemcpyAsync(&last[1], d_keep + (P - 1), sizeof(int32_t), hipMemcpyDeviceToHost, q));
-        PREP_HIP(hipMemcpyAsync(&last[2], d_err, sizeof(int32_t), hipMemcpyDeviceToHost, q));
+        PREP_HIP(hipMemcpyAsync(&last[2], d_err, 2 * sizeof(int32_t), hipMemcpyDeviceToHost, q));
         PREP_HIP(hipStreamSynchronize(q));
         if (last[2]) return CELESTE_PREP_ERR_INVALID_ARG;       // a tried pair without a positive flux, or a NaN radius
         E = (int64_t)last[0] + last[1];
+        if (max_rows < 0) max_rows = std::max(last[3], 1);
     }
     PrepEntries D;
     memset(&D, 0, sizeof D);
@@ -743,6 +793,7 @@ extern "C" int celeste_prep_patches(celeste_prep_images_t *handle, int64_t n_sou
                  o_noff = carve(&at, (size_t)(S + 1) * 8), o_nbr = carve(&at, (size_t)R * 4),
                  o_stamp = carve(&at, want_stamps ? (size_t)E * 4 : 0),
                  o_stamps = carve(&at, want_stamps ? (size_t)n_stamps * PREP_NPIX * 8 : 0);
+    for (int i = 0; i < n_extra; ++i) extra[i].at = carve(&at, extra[i].bytes);
     size_t got = 0;
     char *blk = (char *)pinned_take(std::max<size_t>(at, 256), &got);
     if (!blk) return CELESTE_PREP_ERR_ALLOC;
@@ -754,6 +805,7 @@ extern "C" int celeste_prep_patches(celeste_prep_images_t *handle, int64_t n_sou
     PREP_DOWN(o_pc, D.pc, (size_t)E * 16); PREP_DOWN(o_wc, D.wc, (size_t)E * 16); PREP_DOWN(o_active, d_active, (size_t)E * 8);
     PREP_DOWN(o_noff, d_noff, (size_t)(S + 1) * 8); PREP_DOWN(o_nbr, d_nbr, (size_t)R * 4);
     if (want_stamps) { PREP_DOWN(o_stamp, d_stamp, (size_t)E * 4); PREP_DOWN(o_stamps, d_stamps, (size_t)n_stamps * PREP_NPIX * 8); }
+    for (int i = 0; i < n_extra; ++i) { PREP_DOWN(extra[i].at, extra[i].dptr, extra[i].bytes); extra[i].host = blk + extra[i].at; }
 #undef PREP_DOWN
     if (!hst && hipStreamSynchronize(q) != hipSuccess) hst = 1;
     if (hst) {
@@ -791,6 +843,7 @@ extern "C" int celeste_prep_bad_sky(celeste_prep_images_t *handle, int64_t n, co
     if (st) return st;
     hipStream_t q = call.stream;
     for (float &m : g_last_ms) m = 0.0f;
+    for (float &m : g_det_ms) m = 0.0f;
     double *d_pos; uint8_t *d_flags;
     if ((st = call.alloc(&d_pos, (size_t)n * 2)) || (st = call.alloc(&d_flags, (size_t)n))) return st;
     PREP_HIP(hipMemcpyAsync(d_pos, pos, (size_t)n * 2 * sizeof(double), hipMemcpyHostToDevice, q));
@@ -803,3 +856,5 @@ extern "C" int celeste_prep_bad_sky(celeste_prep_images_t *handle, int64_t n, co
     (void)hipEventElapsedTime(&g_last_ms[4], call.ev[0], call.ev[1]);
     return CELESTE_PREP_OK;
 }
+
+#include "prep_detected.h"

@@ -134,12 +134,13 @@ def _image_arrays(img):
 
 def extract(images, device: int = 0, thresh: float = 1.3, minarea: int = 5, deblend_nthresh: int = 32,
             deblend_cont: float = 0.005, want_maps: bool = False, lds_max_pixels: int = 0,
-            stage_ms: Optional[dict] = None) -> List[Catalog]:
+            stage_ms: Optional[dict] = None, want_pixels: bool = True) -> List[Catalog]:
     """SEP.Background(cal; boxsize=(256, 256), filtersize=(3, 3)) + global_rms + SEP.extract(cal, thresh; noise=rms)
     (detection.jl:45-58) for every image, in one device call.  `images`: model.Image objects or (pixels, sky,
     nelec_per_nmgy) triples.  SEP's `clean` pass (removal of detections explained by a bright neighbour's wings) is not
     done.  lds_max_pixels > 0 lowers the size limit of the LDS deblending path (components above it take the
-    global-memory path).  stage_ms: a dict that receives the device time of each stage."""
+    global-memory path).  stage_ms: a dict that receives the device time of each stage.  want_pixels=False leaves
+    Catalog.pixels empty (the per-object lists are built by a Python loop that callers of the moments alone do not need)."""
     lib = load_library()
     keep = []
     arr = (ImageT * max(len(images), 1))()
@@ -173,13 +174,13 @@ def extract(images, device: int = 0, thresh: float = 1.3, minarea: int = 5, debl
                     "formats": ["<i4"] * 7 + ["<i8"] + ["<f8"] * 10,
                     "offsets": [getattr(ObjectT, f[0]).offset for f in ObjectT._fields_],
                     "itemsize": C.sizeof(ObjectT)}))
-                pix = np.ctypeslib.as_array(R.pix, shape=(R.n_pix,)).copy()
+                pix = np.ctypeslib.as_array(R.pix, shape=(R.n_pix,)).copy() if want_pixels else None
             else:
                 rec = np.zeros(0, dtype=[(f[0], "<f8") for f in ObjectT._fields_])
                 pix = np.zeros(0, dtype=np.int64)
             H = R.H
             pixels = []
-            for o in range(m):
+            for o in range(m if want_pixels else 0):
                 s = pix[rec["pix_offset"][o]: rec["pix_offset"][o] + rec["npix"][o]]
                 pixels.append(np.stack([s % H, s // H], axis=1))
             ints = {k: np.asarray(rec[k], dtype=np.int64) for k in ("npix", "xmin", "xmax", "ymin", "ymax", "parent")}
@@ -307,3 +308,12 @@ def detect_sources(images, device: int = 0, match_radius: float = 1.0 / 3600.0, 
     (overlapping) images, one CatalogEntry and one row of ImagePatches per joined object."""
     catalogs = extract(images, device=device, **extract_kw)
     return build_detection_output(images, catalogs, match_radius)
+
+
+def detect_table(images, device: int = 0, match_radius: float = 1.0 / 3600.0, prep_images=None, **extract_kw):
+    """detect_sources with everything behind the extraction on the device too (prep.detected_table): (catalog, table) -- the
+    catalog of detect_sources and, in place of its ImagePatch rows, their model.PatchTable with neighbour lists (and the
+    stamps of eigen-PSF images), which cabi.problem_from_table takes.  prep_images: a prep.PrepImages over `images`."""
+    from . import prep
+    catalogs = extract(images, device=device, want_pixels=False, **extract_kw)
+    return prep.detected_table(images, catalogs, match_radius, device=device, prep_images=prep_images)

@@ -309,12 +309,16 @@ def infer_box(images, box: BoundingBox, catalog=None, method: str = "joint_vi", 
     inside the library); None = the one `device`.
     prep: "host" builds the patch table, the neighbour lists, the stamps of a variable PSF and the sky flags of a catalog on
     the host (model.patch_table, infer.bad_sky_flags); "device" builds them on the device (prep.patch_table,
-    prep.bad_sky_flags: one upload of the planes serves both).  Detection (catalog=None) brings its own patches either way."""
+    prep.bad_sky_flags: one upload of the planes serves both).  Without a catalog, "host" joins the detections and builds the
+    catalog and the patches on the host (detect.detect_sources), "device" on the device (detect.detect_table: the patch table,
+    the neighbour lists and the sky flags from one upload of the planes)."""
     if prep not in ("host", "device"):
         raise ValueError("prep must be 'host' or 'device', not %r" % (prep,))
     if method == "mcmc" and devices is not None:
         raise ValueError("method='mcmc' runs on one device: pass device=..., not devices=... (device groups run VI only)")
     if catalog is None:
+        if prep == "device":
+            return _infer_box_detected_table(images, box, method, cfg, n_iters, device, schedule, devices, match_radius, mcmc_config)
         return _infer_box_detected(images, box, method, cfg, n_iters, device, schedule, devices, match_radius, mcmc_config)
     targets = [i for i, ce in enumerate(catalog) if box.contains(ce.pos)]
     if not targets:
@@ -432,5 +436,56 @@ def _infer_box_detected(images, box: BoundingBox, method, cfg, n_iters, device, 
             ctx.close()
         flag_device = device
     flags = bad_sky_flags([catalog[t] for t in targets], images, flag_device)
+    return [OptimizedSource(float(catalog[t].pos[0]), float(catalog[t].pos[1]), vs[k].copy(), flags[k], t in failed)
+            for k, t in enumerate(targets)]
+
+
+def _infer_box_detected_table(images, box: BoundingBox, method, cfg, n_iters, device, schedule, devices,
+                              match_radius, mcmc_config=None) -> list:
+    """_infer_box_detected with the join, the catalog, the patch table, the neighbour lists and the sky flags from the device
+    (detect.detect_table, prep.bad_sky_flags over one prep.PrepImages); the problem is cabi.problem_from_table's."""
+    from . import cabi, prep
+    from .detect import detect_table
+    if method not in ("joint_vi", "single_vi", "mcmc"):
+        raise ValueError("unknown method: %s" % method)
+    if devices is not None and schedule != "cyclades":
+        raise ValueError("a device group runs the reference's Cyclades schedule")
+    first = devices[0] if devices is not None else device
+    with prep.PrepImages(images, first) as pi:
+        catalog, table = detect_table(images, device=first, match_radius=match_radius, prep_images=pi)
+        targets = [i for i, ce in enumerate(catalog) if box.contains(ce.pos)]
+        if not targets:
+            return []
+        neighbors = table.neighbors()
+        problem = cabi.problem_from_table(images, table, neighbors)
+        failed: set = set()
+        if method == "mcmc":
+            from .mcmc import MCMCContext, run_ais_batch
+            mc = MCMCContext(problem, device)
+            try:
+                return run_ais_batch(mc, catalog, targets, mcmc_config)
+            finally:
+                mc.close()
+        if devices is not None:
+            from .group import FieldGroup
+            group = FieldGroup(images, None, neighbors, devices=list(devices), problem=problem)
+            try:
+                if method == "joint_vi":
+                    vs = group_joint_infer(group, catalog, targets, neighbors, cfg, n_iters=n_iters, failed=failed)
+                else:
+                    vs = group_single_infer(group, catalog, targets, cfg, failed=failed)
+            finally:
+                group.close()
+        else:
+            ctx = FieldContext(images, None, neighbors, device=device, problem=problem)
+            try:
+                if method == "joint_vi":
+                    vs = one_node_joint_infer(ctx, catalog, targets, neighbors, cfg, n_iters=n_iters, schedule=schedule,
+                                              failed=failed)
+                else:
+                    vs = one_node_single_infer(ctx, catalog, targets, cfg, failed=failed)
+            finally:
+                ctx.close()
+        flags = prep.bad_sky_flags([catalog[t] for t in targets], images, prep_images=pi)
     return [OptimizedSource(float(catalog[t].pos[0]), float(catalog[t].pos[1]), vs[k].copy(), flags[k], t in failed)
             for k, t in enumerate(targets)]

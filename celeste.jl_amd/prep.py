@@ -6,6 +6,7 @@
   PatchTable.neighbors (find_neighbors for every source)     table.neighbor_lists (the same call)
   SDSSPSFMap.__call__ at every patch centre                  table.stamp / table.stamps (the same call)
   infer.bad_sky per catalog entry                            bad_sky_flags        (celeste_prep_bad_sky)
+  detect.build_detection_output + model.neighbor_map         detected_table       (celeste_prep_detected)
 
 `PrepImages` uploads the planes once (numpy's row-major H x W arrays as they are) and serves any number of calls;
 patch_table and bad_sky_flags make one of their own when none is given.  include/celeste_prep.h and DESIGN.md section 14
@@ -22,17 +23,24 @@ import numpy as np
 
 from . import cabi
 from .model import PatchTable, SDSSPSFMap, get_psf_width
+from .params import CatalogEntry
 
 LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc", "prep", "libceleste_prep.so")
 ABI_VERSION = 100          # CELESTE_PREP_ABI_VERSION of include/celeste_prep.h
 EXPORTED_SYMBOLS = ["celeste_prep_version", "celeste_prep_strerror", "celeste_prep_images_create", "celeste_prep_images_destroy",
                     "celeste_prep_patches", "celeste_prep_result_get", "celeste_prep_result_destroy", "celeste_prep_bad_sky",
-                    "celeste_prep_last_ms"]
+                    "celeste_prep_last_ms", "celeste_prep_detected_check", "celeste_prep_detected",
+                    "celeste_prep_result_get_catalog", "celeste_prep_detected_last_ms"]
 ERR_INVALID_ARG, ERR_NO_DEVICE, ERR_HIP, ERR_ALLOC = 1, 2, 3, 4
 FLAG_DENSE, FLAG_STAMPS = 1, 2
 STAMP = 51                 # CELESTE_PREP_STAMP
 N_STAGES = 5               # CELESTE_PREP_N_STAGES
 STAGES = ("geometry", "active_pixels", "neighbors", "stamps", "sky")
+MATCH_TILE = 1024          # CELESTE_PREP_MATCH_TILE: joined positions per LDS tile of the match kernel
+MATCH_BLOCK = 256          # CELESTE_PREP_MATCH_BLOCK: detections per workgroup of the match kernel
+DETECTED_N_STAGES = 6      # CELESTE_PREP_DETECTED_N_STAGES
+DETECTED_STAGES = ("join", "entries", "geometry", "active_pixels", "neighbors", "stamps")
+MIN_RADIUS_PIX, DILATE = 5.0, 0.2     # detection.jl:152-167
 
 c_float_p, c_double_p = C.POINTER(C.c_float), C.POINTER(C.c_double)
 
@@ -67,6 +75,25 @@ class PrepTableT(C.Structure):
                 ("stamps", c_double_p)]
 
 
+class PrepDetectionT(C.Structure):
+    """celeste_prep_detection_t"""
+    _fields_ = [("npix", C.c_int32), ("xmin", C.c_int32), ("xmax", C.c_int32), ("ymin", C.c_int32), ("ymax", C.c_int32),
+                ("reserved", C.c_int32), ("x", C.c_double), ("y", C.c_double), ("a", C.c_double), ("b", C.c_double),
+                ("theta", C.c_double), ("flux", C.c_double)]
+
+
+DETECTION_DTYPE = np.dtype([("npix", "<i4"), ("xmin", "<i4"), ("xmax", "<i4"), ("ymin", "<i4"), ("ymax", "<i4"), ("reserved", "<i4"),
+                            ("x", "<f8"), ("y", "<f8"), ("a", "<f8"), ("b", "<f8"), ("theta", "<f8"),
+                            ("flux", "<f8")])   # celeste_prep_detection_t, field for field
+
+
+class PrepCatalogT(C.Structure):
+    """celeste_prep_catalog_t"""
+    _fields_ = [("n_objects", C.c_int64), ("n_detections", C.c_int64), ("pos", c_double_p), ("flux", c_double_p),
+                ("gal_axis_ratio", c_double_p), ("gal_angle", c_double_p), ("gal_radius_px", c_double_p),
+                ("det_offsets", C.POINTER(C.c_int64)), ("det_image", C.POINTER(C.c_int32)), ("det_object", C.POINTER(C.c_int32))]
+
+
 class PrepError(RuntimeError):
     def __init__(self, status: int, text: str):
         super().__init__("libceleste_prep: %s (status %d)" % (text, status))
@@ -91,7 +118,7 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     if lib.celeste_prep_version() // 100 != ABI_VERSION // 100:
         raise ImportError("%s has ABI version %d, this binding was written against %d" % (path, lib.celeste_prep_version(),
                                                                                            ABI_VERSION))
-    assert SOURCE_DTYPE.itemsize == C.sizeof(PrepSourceT)
+    assert SOURCE_DTYPE.itemsize == C.sizeof(PrepSourceT) and DETECTION_DTYPE.itemsize == C.sizeof(PrepDetectionT)
     vp = C.c_void_p
     lib.celeste_prep_strerror.restype = C.c_char_p
     lib.celeste_prep_strerror.argtypes = [C.c_int]
@@ -109,6 +136,14 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.celeste_prep_bad_sky.argtypes = [vp, C.c_int64, c_double_p, C.POINTER(C.c_uint8)]
     lib.celeste_prep_last_ms.restype = C.c_int
     lib.celeste_prep_last_ms.argtypes = [c_float_p]
+    lib.celeste_prep_detected_check.restype = C.c_int
+    lib.celeste_prep_detected_check.argtypes = [C.c_int32, vp, vp, vp, C.c_double, C.c_double, C.c_double, C.c_uint32]
+    lib.celeste_prep_detected.restype = C.c_int
+    lib.celeste_prep_detected.argtypes = [vp, vp, vp, vp, C.c_double, C.c_double, C.c_double, C.c_uint32, C.POINTER(vp)]
+    lib.celeste_prep_result_get_catalog.restype = C.c_int
+    lib.celeste_prep_result_get_catalog.argtypes = [vp, C.POINTER(PrepCatalogT)]
+    lib.celeste_prep_detected_last_ms.restype = C.c_int
+    lib.celeste_prep_detected_last_ms.argtypes = [c_float_p]
     if path == LIB_PATH or path == os.environ.get("CELESTE_MI355X_PREP_LIB"):
         _lib = lib
     return lib
@@ -124,6 +159,13 @@ def last_ms() -> dict:
     ms = (C.c_float * N_STAGES)()
     load_library().celeste_prep_last_ms(ms)
     return {k: float(v) for k, v in zip(STAGES, ms)}
+
+
+def detected_last_ms() -> dict:
+    """device milliseconds of the stages of the last call, when it was detected_table, by name (DETECTED_STAGES)"""
+    ms = (C.c_float * DETECTED_N_STAGES)()
+    load_library().celeste_prep_detected_last_ms(ms)
+    return {k: float(v) for k, v in zip(DETECTED_STAGES, ms)}
 
 
 def _plane(a):
@@ -256,21 +298,82 @@ def patch_table(images, catalog, radius_override_pix: float = math.nan, sparse: 
         _check(lib, lib.celeste_prep_patches(pi.handle, len(src), src.ctypes.data_as(C.c_void_p), float(radius_override_pix),
                                              flags, C.byref(rh)))
         res = _Result(lib, rh)
-        t = PrepTableT()
-        _check(lib, lib.celeste_prep_result_get(rh, C.byref(t)))
-        E, S = int(t.n_entries), int(t.n_sources)
-        table = PatchTable(S, len(images), not sparse,
-                           _view(t.source, (E,), np.int32).copy(), _view(t.image, (E,), np.int32).copy(),
-                           _view(t.box, (E, 4), np.int64).copy(), _view(t.pixel_center, (E, 2), np.float64).copy(),
-                           _view(t.world_center, (E, 2), np.float64).copy(), _view(t.active_pixels, (E,), np.int64).copy())
-        off = _view(t.nbr_offsets, (S + 1,), np.int64).tolist()
-        idx = _view(t.nbr_index, (int(t.n_neighbors),), np.int32).tolist()
-        table.neighbor_lists = [idx[off[s]:off[s + 1]] for s in range(S)]
-        if pi.has_eigen_psf:
-            table.stamp = _view(t.stamp, (E,), np.int32).copy()
-            table.stamps = _view(t.stamps, (int(t.n_stamps), STAMP * STAMP), np.float64)   # a view: no copy of the stamps
-            table._prep_result = res      # (owns the memory of `stamps`)
+        table = _table_from_result(lib, rh, res, len(images), sparse, pi.has_eigen_psf)
         return table
+    finally:
+        if own:
+            pi.close()
+
+
+def _table_from_result(lib, rh, res, n_images: int, sparse: bool, with_stamps: bool) -> PatchTable:
+    t = PrepTableT()
+    _check(lib, lib.celeste_prep_result_get(rh, C.byref(t)))
+    E, S = int(t.n_entries), int(t.n_sources)
+    table = PatchTable(S, n_images, not sparse,
+                       _view(t.source, (E,), np.int32).copy(), _view(t.image, (E,), np.int32).copy(),
+                       _view(t.box, (E, 4), np.int64).copy(), _view(t.pixel_center, (E, 2), np.float64).copy(),
+                       _view(t.world_center, (E, 2), np.float64).copy(), _view(t.active_pixels, (E,), np.int64).copy())
+    off = _view(t.nbr_offsets, (S + 1,), np.int64).tolist()
+    idx = _view(t.nbr_index, (int(t.n_neighbors),), np.int32).tolist()
+    table.neighbor_lists = [idx[off[s]:off[s + 1]] for s in range(S)]
+    if with_stamps:
+        table.stamp = _view(t.stamp, (E,), np.int32).copy()
+        table.stamps = _view(t.stamps, (int(t.n_stamps), STAMP * STAMP), np.float64)   # a view: no copy of the stamps
+        table._prep_result = res      # (owns the memory of `stamps`)
+    return table
+
+
+def detection_table(catalogs):
+    """(det_offsets [n_images + 1] int64, the celeste_prep_detection_t array) of per-image detect.Catalog objects"""
+    off = np.zeros(len(catalogs) + 1, dtype=np.int64)
+    off[1:] = np.cumsum([len(c) for c in catalogs])
+    det = np.zeros(int(off[-1]), dtype=DETECTION_DTYPE)
+    for n, c in enumerate(catalogs):
+        d = det[off[n]:off[n + 1]]
+        for k in ("npix", "xmin", "xmax", "ymin", "ymax", "x", "y", "a", "b", "theta", "flux"):
+            d[k] = getattr(c, k)
+    return off, det
+
+
+def detected_table(images, catalogs, match_radius: float, sparse: Optional[bool] = None, device: int = 0,
+                   prep_images: Optional[PrepImages] = None):
+    """detect.build_detection_output and model.neighbor_map on the device: (catalog, table) of the per-image detect.Catalog
+    objects `catalogs`.  catalog: the CatalogEntry list of the joined objects (detect.match_detections, detect.catalog_entry);
+    table: their model.PatchTable with the boxes of detect.detection_box, `neighbor_lists`, `stamp` / `stamps` when an image
+    has an SDSSPSFMap (as patch_table returns them) and `detections`, one list of (image, object) per joined object.
+    sparse=None: build_detection_output's rule, more than 8 images."""
+    from .detect import x_vs_n_angle
+    if len(catalogs) != len(images):
+        raise ValueError("one catalog per image: %d catalogs, %d images" % (len(catalogs), len(images)))
+    if sparse is None:
+        sparse = len(images) > 8
+    own = prep_images is None
+    pi = PrepImages(images, device) if own else prep_images
+    try:
+        lib = pi.lib
+        assert len(pi.images) == len(images)
+        off, det = detection_table(catalogs)
+        ang = np.array([x_vs_n_angle(im.wcs_jacobian) for im in images], dtype=np.float64)
+        flags = (0 if sparse else FLAG_DENSE) | (FLAG_STAMPS if pi.has_eigen_psf else 0)
+        rh = C.c_void_p()
+        _check(lib, lib.celeste_prep_detected(pi.handle, off.ctypes.data_as(C.c_void_p), det.ctypes.data_as(C.c_void_p),
+                                              ang.ctypes.data_as(C.c_void_p), float(match_radius), MIN_RADIUS_PIX, DILATE, flags,
+                                              C.byref(rh)))
+        res = _Result(lib, rh)
+        table = _table_from_result(lib, rh, res, len(images), sparse, pi.has_eigen_psf)
+        k = PrepCatalogT()
+        _check(lib, lib.celeste_prep_result_get_catalog(rh, C.byref(k)))
+        S, D = int(k.n_objects), int(k.n_detections)
+        pos = _view(k.pos, (S, 2), np.float64).copy()
+        flux = _view(k.flux, (S, 5), np.float64).copy()
+        ratio = _view(k.gal_axis_ratio, (S,), np.float64).tolist()
+        angle = _view(k.gal_angle, (S,), np.float64).tolist()
+        radius = _view(k.gal_radius_px, (S,), np.float64).tolist()
+        catalog = [CatalogEntry(pos[s], False, flux[s].copy(), flux[s], 0.5, ratio[s], angle[s], radius[s]) for s in range(S)]
+        doff = _view(k.det_offsets, (S + 1,), np.int64).tolist()
+        pairs = list(zip(_view(k.det_image, (D,), np.int32).tolist(), _view(k.det_object, (D,), np.int32).tolist()))
+        table.detections = [pairs[doff[s]:doff[s + 1]] for s in range(S)]
+        return catalog, table
     finally:
         if own:
             pi.close()

@@ -41,6 +41,29 @@
  *     median = the k-th smallest (0-based) for odd n, (the (k-1)-th + the k-th) * 0.5f in Float32 for even n,
  *     by an 8-bit radix select on ordered keys;  flag = n > 0 and claimed + 5 < (double)median.
  *
+ * Detections (celeste_prep_detected): the per-image objects of source extraction become joined objects, one catalog entry
+ * per object and the patch table of those objects, as detection.jl:61-171 builds them; the order of every list is fixed.
+ *     World position of a detection of image n, one thread per detection: J^-1 ((x, y) - pix0) + world0, by the LU above.
+ *     Join: the joined list starts empty; the images are taken in turn.  Every detection of an image looks for the nearest
+ *         entry of the list as it stood before that image: d = sqrt(dx dx + dy dy), dx and dy the differences of the world
+ *         coordinates; the lowest index among equal distances.  d < match_radius: the detection joins that entry (two
+ *         detections of one image may join the same entry, none joins an entry of its own image); otherwise it is
+ *         appended, in object order.  So image 0's detections open the list in object order.  One match launch per image
+ *         (a thread per detection, the list through LDS in tiles of CELESTE_PREP_MATCH_TILE) and one scan-and-append
+ *         launch; the length of the list stays on the device between them.  The search is exhaustive.
+ *     Detections of an object: in (image, object) order -- a stable radix sort of the detections by joined index.
+ *     Catalog entry, one thread per object: per band the detection with the most pixels (strict >: the first wins a tie);
+ *         flux[b] = its flux, 0 for a band without a detection; the shape comes from the best detection of the band with
+ *         the largest best npix (the first band on a tie): gal_axis_ratio = b / a, gal_angle = theta + x_vs_n_angle[image],
+ *         gal_radius_px = sqrt(a b) C4, C4 = sqrt(2 log 2) evaluated once by the host's libm.  (is_star is false and
+ *         gal_frac_dev 0.5 for every entry; the star's fluxes are the galaxy's.)
+ *     Box of (object, image), one thread per pair: pc of the joined position as above; minbox = rows rint(pc1 - m) ..
+ *         rint(pc1 + m), columns likewise with pc2, m = min_radius_pix.  With a detection of the object in that image (the
+ *         last one in object order): its xmin .. xmax are read as a 1-based row range, ymin .. ymax as a column range, each
+ *         widened on both sides by rint((dilate length) / 2), length = last - first + 1; the box is the smallest that
+ *         holds the widened ranges and minbox.  Without one the box is minbox.  Then clamp_box.  An entry for every pair
+ *         (DENSE) or for the pairs whose clamped box holds a pixel; from there on as for celeste_prep_patches.
+ *
  * Thread safety: calls are serialised inside the library.  Without a HIP device the entry points that compute return
  * CELESTE_PREP_ERR_NO_DEVICE -- there is no CPU path.  Invalid arguments are refused before any HIP call (the flux and NaN
  * checks above are part of the geometry kernel and are reported when it has run). */
@@ -58,6 +81,9 @@ extern "C" {
 #define CELESTE_PREP_MAX_POLY 8        /* ni, nj <= 8 */
 #define CELESTE_PREP_MAX_NK 16         /* nk <= 16 */
 #define CELESTE_PREP_N_STAGES 5        /* celeste_prep_last_ms */
+#define CELESTE_PREP_MATCH_TILE 1024   /* joined positions per LDS tile of the match kernel */
+#define CELESTE_PREP_MATCH_BLOCK 256   /* detections per workgroup of the match kernel */
+#define CELESTE_PREP_DETECTED_N_STAGES 6   /* celeste_prep_detected_last_ms */
 
 enum {
     CELESTE_PREP_OK = 0,
@@ -114,6 +140,28 @@ typedef struct celeste_prep_table_t {
     const double *stamps;            /* [n_stamps][51 * 51], column-major raw stamps; NULL without FLAG_STAMPS */
 } celeste_prep_table_t;
 
+/* one object of one image, SEP's axes: x runs along axis 0 (rows) */
+typedef struct celeste_prep_detection_t {
+    int32_t npix;
+    int32_t xmin, xmax, ymin, ymax;  /* 0-based, inclusive, as celeste_detect_object_t */
+    int32_t reserved;
+    double x, y;                     /* 1-based centroid */
+    double a, b, theta, flux;
+} celeste_prep_detection_t;
+
+/* page-locked host arrays owned by the result; S = n_objects, the sources of the result's table in the same order */
+typedef struct celeste_prep_catalog_t {
+    int64_t n_objects, n_detections;
+    const double *pos;               /* [S][2] */
+    const double *flux;              /* [S][5] */
+    const double *gal_axis_ratio;    /* [S] */
+    const double *gal_angle;         /* [S] */
+    const double *gal_radius_px;     /* [S] */
+    const int64_t *det_offsets;      /* [S + 1] */
+    const int32_t *det_image;        /* [n_detections]: the detections of s are det_offsets[s] .. det_offsets[s + 1], */
+    const int32_t *det_object;       /* [n_detections]  image ascending, within an image the object index ascending */
+} celeste_prep_catalog_t;
+
 typedef struct celeste_prep_images celeste_prep_images_t;
 typedef struct celeste_prep_result celeste_prep_result_t;
 
@@ -131,12 +179,31 @@ int celeste_prep_patches(celeste_prep_images_t *handle, int64_t n_sources, const
 int celeste_prep_result_get(const celeste_prep_result_t *result, celeste_prep_table_t *table);
 void celeste_prep_result_destroy(celeste_prep_result_t *result);
 
+/* The argument checks of celeste_prep_detected that need no handle: INVALID_ARG for a null pointer, offsets that do not
+ * ascend from 0, npix <= 0, a non-finite x, y, a, b, theta, flux or angle, a <= 0, xmax < xmin, ymax < ymin, a match_radius
+ * that is NaN or negative, a min_radius_pix or dilate that is not finite or is negative, an unknown flag. */
+int celeste_prep_detected_check(int32_t n_images, const int64_t *det_offsets, const celeste_prep_detection_t *dets,
+                                const double *x_vs_n_angle, double match_radius, double min_radius_pix, double dilate,
+                                uint32_t flags);
+
+/* The joined objects of the detections dets[det_offsets[n] .. det_offsets[n + 1]) of image n of `handle`, their catalog
+ * entries and their patch table (neighbour lists and, with FLAG_STAMPS, stamps included).  detection.jl uses
+ * min_radius_pix = 5 and dilate = 0.2.  No detection at all: OK, zero objects, an empty table. */
+int celeste_prep_detected(celeste_prep_images_t *handle, const int64_t *det_offsets, const celeste_prep_detection_t *dets,
+                          const double *x_vs_n_angle, double match_radius, double min_radius_pix, double dilate,
+                          uint32_t flags, celeste_prep_result_t **result);
+/* INVALID_ARG for a result that does not come from the call above */
+int celeste_prep_result_get_catalog(const celeste_prep_result_t *result, celeste_prep_catalog_t *catalog);
+
 /* flags[i] = the sky check of pos[2 i], pos[2 i + 1], i < n */
 int celeste_prep_bad_sky(celeste_prep_images_t *handle, int64_t n, const double *pos, uint8_t *flags);
 
 /* device time of the stages of the last call of this process, in milliseconds: geometry and compaction, active pixels,
  * neighbours, stamps (celeste_prep_patches; the sky check's slot is 0), sky check (celeste_prep_bad_sky; the others 0) */
 int celeste_prep_last_ms(float ms[CELESTE_PREP_N_STAGES]);
+/* the same for the last call that took detections: world positions, join and sort; catalog entries; then the four table
+ * stages as above (0 after any other call) */
+int celeste_prep_detected_last_ms(float ms[CELESTE_PREP_DETECTED_N_STAGES]);
 
 #ifdef __cplusplus
 }
