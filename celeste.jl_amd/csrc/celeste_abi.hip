@@ -203,6 +203,7 @@ struct celeste_ctx {
     int32_t *d_prep_mark = nullptr; // per source: stamp of the last batch that read its per-image tables
     double *d_lg_sum = nullptr;     // per visit: sum of lgamma(pixel + 1) over the patch's visited pixels
     int64_t *d_nv_base = nullptr;   // visit-list mode: per source, start of its rows in d_nbr_vis
+    std::vector<int64_t> h_nv_base; // its host mirror (a prepared list describes its work items from it)
     int32_t *d_nbr_vis = nullptr;   // visit-list mode: [visit of s][neighbour of s] -> the neighbour's visit in that image
     int2 *d_items = nullptr;         // [ti * M + j] of the current batch: {visit, image}
     size_t items_cap = 0;
@@ -644,6 +645,7 @@ extern "C" int celeste_ctx_create_on(celeste_images_t *imgs, const celeste_probl
         }
         CTX_TRY(dev_upload(&c->d_nv_base, base.data(), base.size()));
         CTX_TRY(dev_upload(&c->d_nbr_vis, nv.data(), nv.size()));
+        c->h_nv_base.swap(base);
     }
     {
         std::vector<int32_t> sorted(c->h_src_chunks);
@@ -1140,13 +1142,17 @@ struct celeste_targets {
     int64_t n_visits = 0, n_vitems = 0, n_uitems = 0;
     int64_t n_records = 0;              // chunk records of a sweep (exact)
     int32_t n_work = 0;                 // work items of pixel_kernel (exact: its grid)
+    // the same items, each described once (work_sequences.h): one workgroup of pixel_desc_kernel per descriptor;
+    // CELESTE_NO_SEQUENCES=1 (the A/B switch) runs pixel_kernel over d_work instead
+    WorkSeqDesc *d_desc = nullptr;      // one 64-byte descriptor per item that has pixels, most trips first
+    int32_t n_desc = 0;
 };
 static const int32_t LIST_STAMP = 1;
 
 static void targets_free(celeste_targets *t) {
     if (!t) return;
     void *ptrs[] = {t->d_targets, t->d_work, t->d_work_total, t->d_rec_off, t->d_items, t->d_needed, t->d_visits, t->d_vitems,
-                    t->d_uitems, t->d_upx};
+                    t->d_uitems, t->d_upx, t->d_desc};
     for (void *p : ptrs) if (p) (void)hipFree(p);
     delete t;
 }
@@ -1221,9 +1227,42 @@ static int targets_build(celeste_ctx_t *c, const std::vector<int32_t> &tg, celes
     LIST_TRY(hipGetLastError());
     LIST_TRY(hipMemcpy(&t->n_work, t->d_work_total, sizeof(int32_t), hipMemcpyDeviceToHost));   // (waits for the kernels)
     LIST_TRY(hipFree(d_blk)); d_blk = nullptr;
+    if (t->n_work < 0 || (int64_t)t->n_work > t->n_records) return fail(CELESTE_ERR_HIP);   // (a group holds at least one record)
+    // The items' descriptors (work_sequences.h): the list's work items and record offsets come back (4 B per item and per
+    // candidate visit) and every item that has pixels is described from the host mirrors as pixel_kernel's prologue would
+    // find it.  Most trips first (ties in work-list order): the work list's own order, without its quantisation.
+    {
+        std::vector<int32_t> h_work((size_t)t->n_work), h_rec_off((size_t)n_cand);
+        if (t->n_work > 0) LIST_TRY(hipMemcpy(h_work.data(), t->d_work, h_work.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+        if (n_cand > 0) LIST_TRY(hipMemcpy(h_rec_off.data(), t->d_rec_off, h_rec_off.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+        std::vector<WorkSeqDesc> items;
+        std::vector<int32_t> trips, order;
+        items.reserve(h_work.size()); trips.reserve(h_work.size());
+        for (int32_t wg0 : h_work) {
+            if (wg0 < 0 || wg0 / c->CH >= n_cand) return fail(CELESTE_ERR_HIP);
+            const int tn = wg0 / c->CH, ch0 = wg0 - tn * c->CH, ti = tn / c->M, j = tn - ti * c->M, s = tg[(size_t)ti];
+            if (j >= c->h_vis_off[s + 1] - c->h_vis_off[s]) continue;       // (pixel_kernel: v < 0)
+            const int32_t v = c->h_vis_off[s] + j;
+            const DevPatch &q = c->h_patches[(size_t)v];
+            const int n_trips = work_item_trips(q.H2 > 0 && q.W2 > 0 ? (int64_t)q.H2 * q.W2 : 0, ch0, t->G, c->chunk_px);
+            if (n_trips <= 0) continue;                                     // (pixel_kernel: empty chunk range)
+            const int64_t nbn = c->h_nbr_off[s + 1] - c->h_nbr_off[s];
+            if (nbn > 0x7fffffffll) return fail(CELESTE_ERR_INVALID_ARG);
+            WorkSeqDesc D{};
+            D.off_h = q.off_h; D.off_w = q.off_w; D.H2 = q.H2; D.W2 = q.W2; D.bitmap_off = q.bitmap_off; D.stamp = q.stamp;
+            D.nb0 = c->h_nbr_off[s]; D.nbn = (int32_t)nbn; D.nv_row = c->dense ? 0 : c->h_nv_base[s] + (int64_t)j * nbn;
+            D.v = v; D.n = c->h_vis_img[(size_t)v]; D.rec_base = h_rec_off[(size_t)tn]; D.ch0 = ch0;
+            order.push_back((int32_t)items.size()); items.push_back(D); trips.push_back(n_trips);
+        }
+        std::stable_sort(order.begin(), order.end(), [&](int32_t a, int32_t b) { return trips[(size_t)a] > trips[(size_t)b]; });
+        std::vector<WorkSeqDesc> sorted(items.size());
+        for (size_t i = 0; i < order.size(); ++i) sorted[i] = items[(size_t)order[i]];
+        t->n_desc = (int32_t)sorted.size();
+        LIST_ALLOC(t->d_desc, std::max<size_t>(sorted.size(), 1) * sizeof(WorkSeqDesc));
+        if (!sorted.empty()) LIST_TRY(hipMemcpy(t->d_desc, sorted.data(), sorted.size() * sizeof(WorkSeqDesc), hipMemcpyHostToDevice));
+    }
 #undef LIST_TRY
 #undef LIST_ALLOC
-    if (t->n_work < 0 || (int64_t)t->n_work > t->n_records) return fail(CELESTE_ERR_HIP);   // (a group holds at least one record)
     c->lists.push_back(t);
     *out = t;
     return CELESTE_OK;
@@ -1316,14 +1355,28 @@ static int launch_prepared(celeste_ctx_t *c, const celeste_targets_t *t, const d
 #undef LAUNCH_VALUE
     }
     if (c->timing) HIP_TRY(hipEventRecord(c->ev[1], stream));
-    const dim3 grid((unsigned)std::max<int32_t>(t->n_work, 1));
+    // one workgroup per described item (pixel_desc_kernel); CELESTE_NO_SEQUENCES=1 (the A/B switch, read per call): pixel_kernel
+    // over the list's d_work
+    const char *no_seq = getenv("CELESTE_NO_SEQUENCES");
+    const bool sequences = !(no_seq && atoi(no_seq) != 0);
+    const dim3 grid((unsigned)std::max<int32_t>(sequences ? t->n_desc : t->n_work, 1));
+#define LAUNCH_SEQ(MODE)                                                                                                    \
+    hipLaunchKernelGGL((pixel_desc_kernel<MODE>), grid, dim3(64), 0, stream, c->d_images, c->d_patches, c->d_coefs,         \
+                       c->d_bitmaps, c->d_srcimg, c->d_comps, c->d_nbr_idx, c->d_val_off, c->d_val, c->N, c->NC, chunk_px,  \
+                       t->G, c->d_acc, t->d_desc, t->n_desc, c->d_nbr_vis, c->d_coefs_f)
+    if (!sequences) { }
+    else if (flags & CELESTE_FLAG_HESS) LAUNCH_SEQ(2);
+    else if (flags & CELESTE_FLAG_GRAD) LAUNCH_SEQ(1);
+    else LAUNCH_SEQ(0);
+#undef LAUNCH_SEQ
 #define LAUNCH_PIXEL(MODE)                                                                                                  \
     hipLaunchKernelGGL((pixel_kernel<MODE, double>), grid, dim3(64), 0, stream, c->d_images, c->d_patches, c->d_coefs,      \
                        c->d_bitmaps, c->d_srcimg, c->d_comps, c->d_nbr_off, c->d_nbr_idx, c->d_val_off, c->d_val,           \
                        t->d_targets, c->N, c->NC, CH, chunk_px, t->G, c->d_acc, c->d_tile_off, c->d_rec,                    \
                        (const int32_t *)nullptr, t->d_items, c->M, t->d_work, t->d_work_total, c->d_nv_base, c->d_nbr_vis,  \
                        t->d_rec_off, c->d_coefs_f)
-    if (flags & CELESTE_FLAG_HESS) LAUNCH_PIXEL(2);
+    if (sequences) { }
+    else if (flags & CELESTE_FLAG_HESS) LAUNCH_PIXEL(2);
     else if (flags & CELESTE_FLAG_GRAD) LAUNCH_PIXEL(1);
     else LAUNCH_PIXEL(0);
 #undef LAUNCH_PIXEL

@@ -19,6 +19,7 @@
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include "elbo_device.h"
+#include "work_sequences.h"
 #include "../../include/celeste_mi355x.h"
 
 // Mutation testing (tests/test_mutants.py builds the library with -DCELESTE_MUTANT=k and checks that the parity
@@ -2424,6 +2425,109 @@ pixel_kernel(const DevImage *__restrict__ images, const DevPatch *__restrict__ p
     __syncthreads();   // the slots are zeroed again for the next chunk of the group
     }
     }   // work item
+}
+
+// ---------------------------------------------------------------------------------------------
+// pixel_desc_kernel: pixel_kernel<MODE, double> over a prepared list's work items, each started from its descriptor
+// (work_sequences.h).  Workgroup b runs item b: the same staging, the same chunk loop over the same pixel_iter and the same
+// records in the same places as pixel_kernel, so the results are its results bit for bit.  What differs is the prologue:
+//  * ONE 64-byte descriptor (a uniform load) where pixel_kernel chases work[item] -> targets / items / rec_off ->
+//    patches[v], nbr_off[t], nv_base[t].  The descriptor's head is laid out as DevPatch's, and the pixel loop reads the
+//    patch's corner, size and bitmap from it: patches[v] is not read at all;
+//  * the loads of srcimg[v], of lane c's own p11, p12, p22 (comp_extra of component c: same expressions, same bits) and of
+//    every round of the staging read are issued together (pixel_kernel's loop waits for each round of 64 doubles in turn);
+//  * the first chunk's slots are zeroed next to the staging: one barrier where there were three.
+// The host describes only items that have pixels (v >= 0, a chunk range that exists): nothing is skipped here.
+// ---------------------------------------------------------------------------------------------
+template <int MODE>
+__global__ void __launch_bounds__(64, PIXEL_WAVES)
+pixel_desc_kernel(const DevImage *__restrict__ images, const DevPatch *__restrict__ patches,
+                  const double *__restrict__ coefs, const uint8_t *__restrict__ bitmaps,
+                  const SrcImg *__restrict__ srcimg, const Comp *__restrict__ comps,
+                  const int32_t *__restrict__ nbr_idx, const int64_t *__restrict__ val_off, const double2 *__restrict__ val,
+                  int N, int NC, int chunk_px, int G, double *__restrict__ acc,
+                  const WorkSeqDesc *__restrict__ desc, int n_items,
+                  const int32_t *__restrict__ nbr_vis, const float *__restrict__ coefs_f) {
+    static_assert(MODE == 0 || MODE == 1 || MODE == 2, "the prepared path: value, gradient, Hessian");
+    static_assert(offsetof(DevPatch, off_h) == offsetof(WorkSeqDesc, off_h) && offsetof(DevPatch, off_w) == offsetof(WorkSeqDesc, off_w) &&
+                  offsetof(DevPatch, H2) == offsetof(WorkSeqDesc, H2) && offsetof(DevPatch, W2) == offsetof(WorkSeqDesc, W2) &&
+                  offsetof(DevPatch, bitmap_off) == offsetof(WorkSeqDesc, bitmap_off) &&
+                  offsetof(DevPatch, stamp) == offsetof(WorkSeqDesc, stamp), "the descriptor's head is DevPatch's");
+    if ((int)blockIdx.x >= n_items) return;  // (an empty list still launches one workgroup)
+    __shared__ double etab[64];
+    __shared__ Comp tc[14 * CEL_MAXK + 1];   // (+ 1: the unrolled component loop requests one record past the last)
+    __shared__ double tcx[MODE == 2 ? COMPX * (14 * CEL_MAXK + 1) : 1];
+    __shared__ double sacc[MODE == 0 ? 1 : ACC_N * ACC_SLOTS];
+    const int lane = threadIdx.x;
+    double *const slot = sacc + (lane & (ACC_SLOTS - 1));
+    const WorkSeqDesc &D = desc[blockIdx.x];
+    const int v = D.v;
+    const SrcImg si = srcimg[v];
+    {
+        constexpr int ROUNDS = (14 * CEL_MAXK * 8 + 63) / 64;
+        const double *src = reinterpret_cast<const double *>(comps + (size_t)v * NC);
+        double *dst = reinterpret_cast<double *>(tc);
+        const double tabv = g_exp2_table[lane];
+        Comp own;
+        if constexpr (MODE == 2) {
+            const Comp &k = comps[(size_t)v * NC + min(lane, NC - 1)];
+            own.p11 = k.p11; own.p12 = k.p12; own.p22 = k.p22;
+        }
+        double r[ROUNDS];     // (clamped, not predicated: straight-line loads; the stores below are predicated)
+#pragma unroll
+        for (int k = 0; k < ROUNDS; ++k) r[k] = src[min(lane + 64 * k, NC * 8 - 1)];
+        if constexpr (MODE == 1 || MODE == 2) {
+#pragma unroll
+            for (int i = 0; i < ACC_N * ACC_SLOTS / 64; ++i) sacc[lane + 64 * i] = 0.0;
+        }
+        etab[lane] = tabv;
+#pragma unroll
+        for (int k = 0; k < ROUNDS; ++k) if (lane + 64 * k < NC * 8) dst[lane + 64 * k] = r[k];
+        if constexpr (MODE == 2) {
+            if (lane < NC) comp_extra(own, tcx + COMPX * lane);
+        }
+        __syncthreads();
+    }
+    PixWork<double> W;
+    // the pixel loop reads off_h, off_w, H2, W2 and bitmap_off of its patch: the descriptor's head
+    W.img = &images[D.n]; W.P = reinterpret_cast<const DevPatch *>(&D); W.patches = patches; W.bitmaps = bitmaps; W.nbr_idx = nbr_idx;
+    W.nb0 = D.nb0; W.nb1 = D.nb0 + D.nbn;
+    W.nv = nbr_vis ? nbr_vis + D.nv_row : nullptr;
+    W.val_off = val_off; W.val = val; W.active_rank = nullptr;
+    W.my_rank = 0;
+    W.N = N; W.n = D.n; W.NC = NC; W.v = v;
+    W.si = si;
+    W.tc = tc; W.tcx = tcx;
+    W.tcr = reinterpret_cast<const CompR<double> *>(tc);
+    W.etab = etab;
+    W.tcoef = coefs + (size_t)(CELESTE_MUTANT == 3 ? 0 : D.stamp) * (CEL_COEF * CEL_COEF);
+    W.tcoef_f = coefs_f + (size_t)(CELESTE_MUTANT == 3 ? 0 : D.stamp) * (CEL_COEF * CEL_COEF);
+    W.tile_off = nullptr; W.rec = nullptr;
+    const int npx = D.H2 * D.W2;
+    const int ch0 = D.ch0;
+    for (int ch = ch0; ch < ch0 + G && ch * chunk_px < npx; ++ch) {   // every chunk of the group writes its own record
+    const int p0 = ch * chunk_px;
+    const int p1 = min(npx, p0 + chunk_px);
+    const int wg = D.rec_base + ch;
+    if constexpr (MODE == 1 || MODE == 2) {
+        if (ch != ch0) {                     // (the first chunk's slots were zeroed with the staging)
+#pragma unroll
+            for (int i = 0; i < ACC_N * ACC_SLOTS / 64; ++i) sacc[lane + 64 * i] = 0.0;
+            __syncthreads();
+        }
+    }
+    double a[3] = {0.0, 0.0, 0.0};
+    for (int base = p0; base < p1; base += 64) pixel_iter<MODE, double, false>(W, base, p1, lane, slot, a, []() {});
+    double *__restrict__ out = acc + (size_t)wg * ACC_N;
+    if (MODE == 0) {
+        const double s0 = wave_sum(a[0]), s1 = wave_sum(a[1]), s2 = wave_sum(a[2]);
+        if (lane == 0) { out[0] = s0; out[ACC_CNT] = s1; out[ACC_CNT + 1] = s2; }
+        continue;
+    }
+    __syncthreads();
+    fold_record_slots<MODE>(sacc, lane, [&](int e, double s) { out[e] = s; });
+    __syncthreads();   // the slots are zeroed again for the next chunk of the group
+    }
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -17,7 +17,10 @@
  * A list also holds the set of neighbour pixels its targets gather, each once (4 bytes per pixel of device memory: 8 MB for
  * 2000 targets of a single field, 138 MB for 30 000 targets of a 4 x 4 grid of fields; CELESTE_ERR_ALLOC if it does not
  * fit), so that a sweep renders a neighbour wanted by several targets once; CELESTE_NO_VALUE_UNION=1 in the environment
- * renders it once per target as celeste_elbo_eval_batch_device does -- same results. */
+ * renders it once per target as celeste_elbo_eval_batch_device does -- same results.
+ * A list holds one 64-byte descriptor per work item of its pixel launch (1.1 MB for the 2000 targets above), from which a
+ * workgroup starts the item without looking it up; CELESTE_NO_SEQUENCES=1 in the environment launches the pixel kernel over
+ * the work list as celeste_elbo_eval_batch_device does -- same results. */
 typedef struct celeste_targets celeste_targets_t;
 int celeste_targets_create(celeste_ctx_t *ctx, int32_t n_targets, const int32_t *targets, celeste_targets_t **out);
 int celeste_targets_create_device(celeste_ctx_t *ctx, int32_t n_targets, const int32_t *d_targets, void *stream,
