@@ -70,9 +70,30 @@ def variational_parameters_to_row(vs: np.ndarray) -> Dict[str, Optional[float]]:
     return row
 
 
-def celeste_to_rows(results) -> List[Dict[str, Optional[float]]]:
-    """one row per OptimizedSource whose sky is not flagged bad"""
-    return [variational_parameters_to_row(r.vs) for r in results if not r.is_sky_bad]
+DIAGNOSTIC_COLUMNS = ("chi2_reduced", "flux_z_r", "purity_r", "max_z", "n_pix")
+
+
+def fit_columns(fit) -> Dict[str, Optional[float]]:
+    """the goodness-of-fit columns of one result (fit.FitStats of infer_box(..., diagnostics=True)): the reduced chi-square
+    and the visited pixels over all bands, the standardised flux misfit and the purity in the r band, the largest pixel
+    deviation; None where the result carries no `fit` or the quantity is undefined"""
+    if fit is None:
+        return {name: None for name in DIAGNOSTIC_COLUMNS}
+
+    def num(x):
+        x = float(x)
+        return x if math.isfinite(x) else None
+    return {"chi2_reduced": num(fit.reduced_chi2()[1]), "flux_z_r": num(fit.flux_z()[2]), "purity_r": num(fit.purity()[2]),
+            "max_z": num(fit.max_z()), "n_pix": int(fit.n_pix.sum())}
+
+
+def celeste_to_rows(results, diagnostics: bool = False) -> List[Dict[str, Optional[float]]]:
+    """one row per OptimizedSource whose sky is not flagged bad; diagnostics: each row also gets DIAGNOSTIC_COLUMNS"""
+    rows = [variational_parameters_to_row(r.vs) for r in results if not r.is_sky_bad]
+    if diagnostics:
+        for row, r in zip(rows, [r for r in results if not r.is_sky_bad]):
+            row.update(fit_columns(getattr(r, "fit", None)))
+    return rows
 
 
 # ---- scoring against a ground-truth catalog (AccuracyBenchmark.jl:140-148, 795-931) -------------------------------
