@@ -499,6 +499,9 @@ def problem_from_table(images, table, neighbors: Optional[Sequence[Sequence[int]
         e = np.flatnonzero(table.image == n)
         J = np.asarray(im.wcs_jacobian, dtype=np.float64)
         arr["wcs_jacobian"][e] = [J[0, 0], J[1, 0], J[0, 1], J[1, 1]]
+        if getattr(table, "wcs_jacobian", None) is not None:      # per-patch Jacobians (some image has a TanWCS)
+            Jp = np.asarray(table.wcs_jacobian, dtype=np.float64)[e]
+            arr["wcs_jacobian"][e] = np.stack([Jp[:, 0, 0], Jp[:, 1, 0], Jp[:, 0, 1], Jp[:, 1, 1]], axis=1)
         psf = np.ascontiguousarray(im.psf, dtype=np.float64)
         assert psf.shape == (psf_K, 6)
         pb._keep.append(psf)

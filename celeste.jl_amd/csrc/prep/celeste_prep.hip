@@ -3,6 +3,7 @@
 //   prep_geometry_kernel     one thread per (source, image) pair: radius, box, clamp; which pairs become entries
 //   prep_compact_kernel      one thread per pair: the kept pairs, in (source, image) order, at their scanned positions;
 //                            centres, the (image, first row) sort key, the eigen-PSF flag
+//   prep_jacobian_kernel     one thread per entry, when an image has a tangent-plane WCS: the finite-difference Jacobian at its centre
 //   prep_active_kernel       one wavefront per entry: the pixels of its box that are not NaN
 //   prep_gather_kernel       boxes and sources in (image, first row) order
 //   prep_nbr_kernel          one thread per entry: the entries of its image whose boxes overlap its own (count, then fill)
@@ -37,7 +38,13 @@ struct PrepImg {
     double J11, J21, J12, J22, w0[2], p0[2], psf_width, eps;
     int32_t ni, nj, nk, pad;
     const double *rrows, *cmat;
+    // celeste_prep_images_set_wcs: kind TAN reads these in place of J, w0, p0 (ci = cd^-1; sin0, cos0 of crval[1]: the host's libm)
+    int32_t kind, pad2;
+    double crval[2], crpix[2], cd[4], ci[4], sin0, cos0;
 };
+
+#define PREP_D2R (M_PI / 180.0)
+#define PREP_R2D (180.0 / M_PI)
 
 struct PrepConsts { double c1, c2, c3; };   // exp(-0.5 * 1.64^2), sqrt(2 pi), 0.5 log(2 pi): the host's libm
 
@@ -49,7 +56,35 @@ __device__ __forceinline__ int32_t round_even(double x) {
 }
 __device__ __forceinline__ int32_t clampi(int32_t v, int32_t lo, int32_t hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
+// the gnomonic projection (celeste_prep.h); NaN behind the tangent plane
+__device__ __forceinline__ void tan_world_to_pix(const PrepImg &im, double ra, double dec, double &pc1, double &pc2) {
+    const double da = (ra - im.crval[0]) * PREP_D2R, dr = dec * PREP_D2R;
+    double sd, cdec, sa, ca;
+    sincos(dr, &sd, &cdec);
+    sincos(da, &sa, &ca);
+    const double l = cdec * sa;
+    // sin dec cos0 - cos dec sin0 cos da as sin(dec - dec0) + 2 cos dec sin0 sin^2(da / 2): no cancellation near the tangent point
+    const double sh = sin(0.5 * da);
+    const double m = sin((dec - im.crval[1]) * PREP_D2R) + (2.0 * (cdec * im.sin0)) * (sh * sh);
+    const double n = sd * im.sin0 + (cdec * im.cos0) * ca;
+    if (!(n > 0.0)) { pc1 = NAN; pc2 = NAN; return; }
+    const double x = (l / n) * PREP_R2D, y = (m / n) * PREP_R2D;
+    pc1 = im.crpix[0] + (im.ci[0] * x + im.ci[1] * y);
+    pc2 = im.crpix[1] + (im.ci[2] * x + im.ci[3] * y);
+}
+
+__device__ __forceinline__ void tan_pix_to_world(const PrepImg &im, double c1, double c2, double &ra, double &dec) {
+    const double u = c1 - im.crpix[0], v = c2 - im.crpix[1];
+    const double x = (im.cd[0] * u + im.cd[1] * v) * PREP_D2R, y = (im.cd[2] * u + im.cd[3] * v) * PREP_D2R;
+    const double den = im.cos0 - y * im.sin0, num = im.sin0 + y * im.cos0;
+    ra = im.crval[0] + atan2(x, den) * PREP_R2D;
+    const double hyp = hypot(x, den);
+    // num cos0 - hyp sin0 = y - sin0 (hyp - den) = y - sin0 x^2 / (hyp + den), without cancellation
+    dec = im.crval[1] + atan2(y - im.sin0 * ((x * x) / (hyp + den)), num * im.sin0 + hyp * im.cos0) * PREP_R2D;
+}
+
 __device__ __forceinline__ void world_to_pix(const PrepImg &im, double x, double y, double &pc1, double &pc2) {
+    if (im.kind == CELESTE_PREP_WCS_TAN) { tan_world_to_pix(im, x, y, pc1, pc2); return; }
     const double d1 = x - im.w0[0], d2 = y - im.w0[1];
     pc1 = (im.J11 * d1 + im.J12 * d2) + im.p0[0];
     pc2 = (im.J21 * d1 + im.J22 * d2) + im.p0[1];
@@ -57,6 +92,7 @@ __device__ __forceinline__ void world_to_pix(const PrepImg &im, double x, double
 
 // J x = (c1, c2) - pix0 by LU with partial pivoting; (w1, w2) = x + world0
 __device__ __forceinline__ void pix_to_world(const PrepImg &im, double c1, double c2, double &w1, double &w2) {
+    if (im.kind == CELESTE_PREP_WCS_TAN) { tan_pix_to_world(im, c1, c2, w1, w2); return; }
     double a11 = im.J11, a12 = im.J12, a21 = im.J21, a22 = im.J22, b1 = c1 - im.p0[0], b2 = c2 - im.p0[1];
     if (fabs(a21) > fabs(a11)) {
         double t = a11; a11 = a21; a21 = t;
@@ -93,7 +129,9 @@ __global__ void __launch_bounds__(PREP_BLOCK) prep_geometry_kernel(const PrepImg
     const bool tried = dense || (pc1 > -reach && pc1 < (double)(im.H + 1) + reach && pc2 > -reach && pc2 < (double)(im.W + 1) + reach);
     if (!tried) { keep[p] = 0; pbox[p] = make_int4(1, 0, 1, 0); return; }
     double r = radius_override;
-    bool bad = !(pc1 == pc1) || !(pc2 == pc2);
+    // (a TAN image: pixel coordinates that are not finite are no error, the pair gets the empty box below)
+    const bool off_plane = im.kind == CELESTE_PREP_WCS_TAN && !(fabs(pc1) < INFINITY && fabs(pc2) < INFINITY);
+    bool bad = !off_plane && (!(pc1 == pc1) || !(pc2 == pc2));
     if (r != r) {     // choose_patch_radius, width_scale 1.2, max_radius 25
         double ow = S.is_star ? 0.0 : 1.2 * S.gal_radius_px / 0.67;
         ow += im.psf_width;
@@ -108,6 +146,7 @@ __global__ void __launch_bounds__(PREP_BLOCK) prep_geometry_kernel(const PrepImg
         if (!(r == r)) bad = true;
     }
     if (bad) { *err = 1; keep[p] = 0; pbox[p] = make_int4(1, 0, 1, 0); return; }
+    if (off_plane) { keep[p] = dense ? 1 : 0; pbox[p] = make_int4(1, 0, 1, 0); return; }
     const int4 b = clamped_box(im, pc1, pc2, r);
     pbox[p] = b;
     keep[p] = (dense || (b.y >= b.x && b.w >= b.z)) ? 1 : 0;
@@ -141,6 +180,28 @@ __global__ void __launch_bounds__(PREP_BLOCK) prep_compact_kernel(const PrepImg 
     E.key[e] = nonempty ? (((unsigned long long)n << 32) | (unsigned long long)(uint32_t)b.x) : ((unsigned long long)N << 32);
     E.val[e] = e;
     E.sflag[e] = (want_stamps && im.has_eig) ? 1 : 0;
+}
+
+// pixel_world_jacobian (wcs_utils.jl:36-51) at (c1, c2), which pix_to_world maps to (w1, w2): J11, J21, J12, J22
+__device__ __forceinline__ void jacobian_at(const PrepImg &im, double c1, double c2, double w1, double w2, double *J) {
+    if (im.kind != CELESTE_PREP_WCS_TAN) { J[0] = im.J11; J[1] = im.J21; J[2] = im.J12; J[3] = im.J22; return; }
+    double s1, s2, a1, a2, b1, b2;
+    tan_pix_to_world(im, c1 + 0.5, c2 + 0.5, s1, s2);
+    const double t1 = fabs(s1 - w1), t2 = fabs(s2 - w2);
+    const double t = t1 > t2 ? t1 : t2;
+    tan_world_to_pix(im, w1 + t, w2, a1, a2);
+    tan_world_to_pix(im, w1, w2 + t, b1, b2);
+    J[0] = (a1 - c1) / t; J[1] = (a2 - c2) / t; J[2] = (b1 - c1) / t; J[3] = (b2 - c2) / t;
+}
+
+// one thread per entry (launched when an image is TAN): the Jacobian at its pixel centre
+__global__ void __launch_bounds__(PREP_BLOCK) prep_jacobian_kernel(const PrepImg *imgs, const int32_t *image, const double *pc, const double *wc,
+                                                                   int64_t E, double *jac) {
+    const int64_t e = (int64_t)blockIdx.x * PREP_BLOCK + threadIdx.x;
+    if (e >= E) return;
+    double J[4];
+    jacobian_at(imgs[image[e]], pc[2 * e], pc[2 * e + 1], wc[2 * e], wc[2 * e + 1], J);
+    jac[4 * e] = J[0]; jac[4 * e + 1] = J[1]; jac[4 * e + 2] = J[2]; jac[4 * e + 3] = J[3];
 }
 
 // one wavefront per entry; lanes run along the contiguous direction of the plane
@@ -322,6 +383,10 @@ __global__ void __launch_bounds__(PREP_BLOCK) prep_sky_kernel(const PrepImg *img
     const int64_t i = blockIdx.x;
     double pc1, pc2;
     world_to_pix(im, pos[2 * i], pos[2 * i + 1], pc1, pc2);
+    if (im.kind == CELESTE_PREP_WCS_TAN && !(fabs(pc1) < INFINITY && fabs(pc2) < INFINITY)) {    // (uniform over the workgroup)
+        if (threadIdx.x == 0) flags[i] = 0;
+        return;
+    }
     const int4 b = clamped_box(im, pc1, pc2, PREP_SKY_RADIUS);
     const int nh = min(max(b.y - b.x + 1, 0), PREP_SKY_SIDE), nw = min(max(b.w - b.z + 1, 0), PREP_SKY_SIDE);
     const int tot = nh * nw;
@@ -378,6 +443,7 @@ struct celeste_prep_images {
     int32_t n_images = 0;
     int sky_image = -1;                 // the first image of band 4
     int any_eig = 0;
+    int any_tan = 0;                    // celeste_prep_images_set_wcs gave an image the kind TAN
     std::vector<PrepImg> host;          // (device pointers inside)
     PrepImg *d_imgs = nullptr;
     std::vector<void *> bufs;
@@ -387,6 +453,7 @@ struct celeste_prep_result {
     void *block = nullptr;              // page-locked
     size_t bytes = 0;
     celeste_prep_table_t table;
+    const double *jac = nullptr;        // [E][4] inside block; null when no image of the handle is TAN
     bool has_catalog = false;
     celeste_prep_catalog_t catalog;
 };
@@ -557,6 +624,49 @@ extern "C" void celeste_prep_images_destroy(celeste_prep_images_t *handle) {
     images_free(handle);
 }
 
+extern "C" int celeste_prep_wcs_check(int32_t n_images, const celeste_prep_wcs_t *wcs) {
+    if (n_images <= 0 || !wcs) return CELESTE_PREP_ERR_INVALID_ARG;
+    for (int n = 0; n < n_images; ++n) {
+        const celeste_prep_wcs_t &w = wcs[n];
+        if (w.kind == CELESTE_PREP_WCS_AFFINE) continue;
+        if (w.kind != CELESTE_PREP_WCS_TAN) return CELESTE_PREP_ERR_INVALID_ARG;
+        for (int k = 0; k < 2; ++k) if (!std::isfinite(w.crval[k]) || !std::isfinite(w.crpix[k])) return CELESTE_PREP_ERR_INVALID_ARG;
+        for (int k = 0; k < 4; ++k) if (!std::isfinite(w.cd[k])) return CELESTE_PREP_ERR_INVALID_ARG;
+        const double det = w.cd[0] * w.cd[3] - w.cd[1] * w.cd[2];
+        if (det == 0.0 || !std::isfinite(det) || std::fabs(w.crval[1]) > 90.0) return CELESTE_PREP_ERR_INVALID_ARG;
+    }
+    return CELESTE_PREP_OK;
+}
+
+extern "C" int celeste_prep_images_set_wcs(celeste_prep_images_t *handle, int32_t n_images, const celeste_prep_wcs_t *wcs) {
+    if (!handle) return CELESTE_PREP_ERR_INVALID_ARG;
+    int st = celeste_prep_wcs_check(n_images, wcs);
+    if (st) return st;
+    if (n_images != handle->n_images) return CELESTE_PREP_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(g_mu);
+    hipStream_t stream;
+    if ((st = prep_stream(handle->device, &stream))) return st;
+    int any_tan = 0;
+    for (int n = 0; n < n_images; ++n) {
+        const celeste_prep_wcs_t &w = wcs[n];
+        PrepImg &D = handle->host[(size_t)n];
+        D.kind = w.kind;
+        if (w.kind != CELESTE_PREP_WCS_TAN) continue;
+        any_tan = 1;
+        const double det = w.cd[0] * w.cd[3] - w.cd[1] * w.cd[2];
+        for (int k = 0; k < 2; ++k) { D.crval[k] = w.crval[k]; D.crpix[k] = w.crpix[k]; }
+        for (int k = 0; k < 4; ++k) D.cd[k] = w.cd[k];
+        D.ci[0] = w.cd[3] / det; D.ci[1] = -w.cd[1] / det; D.ci[2] = -w.cd[2] / det; D.ci[3] = w.cd[0] / det;
+        const double d0 = w.crval[1] * PREP_D2R;
+        D.sin0 = std::sin(d0); D.cos0 = std::cos(d0);
+    }
+    PREP_HIP(hipStreamSynchronize(stream));       // no call of this handle is in flight
+    PREP_HIP(hipMemcpyAsync(handle->d_imgs, handle->host.data(), handle->host.size() * sizeof(PrepImg), hipMemcpyHostToDevice, stream));
+    PREP_HIP(hipStreamSynchronize(stream));
+    handle->any_tan = any_tan;
+    return CELESTE_PREP_OK;
+}
+
 // a page-locked block of `bytes` (from the spare one when it is large enough)
 static void *pinned_take(size_t bytes, size_t *got) {
     if (g_spare && g_spare_bytes >= bytes) {
@@ -584,6 +694,12 @@ static void pinned_give(void *p, size_t bytes) {
 extern "C" int celeste_prep_result_get(const celeste_prep_result_t *result, celeste_prep_table_t *table) {
     if (!result || !table) return CELESTE_PREP_ERR_INVALID_ARG;
     *table = result->table;
+    return CELESTE_PREP_OK;
+}
+
+extern "C" int celeste_prep_result_get_jacobians(const celeste_prep_result_t *result, const double **jac) {
+    if (!result || !jac) return CELESTE_PREP_ERR_INVALID_ARG;
+    *jac = result->jac;
     return CELESTE_PREP_OK;
 }
 
@@ -700,6 +816,14 @@ static int prep_table_stages(celeste_prep_images_t *handle, PrepCall &call, int6
                            want_stamps ? 1 : 0, D);
         PREP_HIP(hipGetLastError());
     }
+    double *d_jac = nullptr;
+    if (handle->any_tan) {
+        if ((st = call.alloc(&d_jac, (size_t)E * 4))) return st;
+        if (E > 0) {
+            hipLaunchKernelGGL(prep_jacobian_kernel, dim3(blocks_for(E)), dim3(PREP_BLOCK), 0, q, handle->d_imgs, D.image, D.pc, D.wc, E, d_jac);
+            PREP_HIP(hipGetLastError());
+        }
+    }
     PREP_HIP(hipEventRecord(call.ev[1], q));
 
     // ---- active pixels
@@ -792,7 +916,8 @@ static int prep_table_stages(celeste_prep_images_t *handle, PrepCall &call, int6
                  o_pc = carve(&at, (size_t)E * 16), o_wc = carve(&at, (size_t)E * 16), o_active = carve(&at, (size_t)E * 8),
                  o_noff = carve(&at, (size_t)(S + 1) * 8), o_nbr = carve(&at, (size_t)R * 4),
                  o_stamp = carve(&at, want_stamps ? (size_t)E * 4 : 0),
-                 o_stamps = carve(&at, want_stamps ? (size_t)n_stamps * PREP_NPIX * 8 : 0);
+                 o_stamps = carve(&at, want_stamps ? (size_t)n_stamps * PREP_NPIX * 8 : 0),
+                 o_jac = carve(&at, d_jac ? (size_t)E * 32 : 0);
     for (int i = 0; i < n_extra; ++i) extra[i].at = carve(&at, extra[i].bytes);
     size_t got = 0;
     char *blk = (char *)pinned_take(std::max<size_t>(at, 256), &got);
@@ -805,6 +930,7 @@ static int prep_table_stages(celeste_prep_images_t *handle, PrepCall &call, int6
     PREP_DOWN(o_pc, D.pc, (size_t)E * 16); PREP_DOWN(o_wc, D.wc, (size_t)E * 16); PREP_DOWN(o_active, d_active, (size_t)E * 8);
     PREP_DOWN(o_noff, d_noff, (size_t)(S + 1) * 8); PREP_DOWN(o_nbr, d_nbr, (size_t)R * 4);
     if (want_stamps) { PREP_DOWN(o_stamp, d_stamp, (size_t)E * 4); PREP_DOWN(o_stamps, d_stamps, (size_t)n_stamps * PREP_NPIX * 8); }
+    if (d_jac) PREP_DOWN(o_jac, d_jac, (size_t)E * 32);
     for (int i = 0; i < n_extra; ++i) { PREP_DOWN(extra[i].at, extra[i].dptr, extra[i].bytes); extra[i].host = blk + extra[i].at; }
 #undef PREP_DOWN
     if (!hst && hipStreamSynchronize(q) != hipSuccess) hst = 1;
@@ -824,6 +950,7 @@ static int prep_table_stages(celeste_prep_images_t *handle, PrepCall &call, int6
     T.nbr_offsets = (const int64_t *)(blk + o_noff); T.nbr_index = (const int32_t *)(blk + o_nbr);
     T.n_neighbors = T.nbr_offsets[S];
     if (want_stamps) { T.stamp = (const int32_t *)(blk + o_stamp); T.stamps = (const double *)(blk + o_stamps); }
+    if (d_jac) res->jac = (const double *)(blk + o_jac);
     for (int i = 0; i < 4; ++i) (void)hipEventElapsedTime(&g_last_ms[i], call.ev[i], call.ev[i + 1]);
     *result = res;
     return CELESTE_PREP_OK;

@@ -2,6 +2,8 @@
 // (include/celeste_prep.h states the arithmetic).  Included at the end of celeste_prep.hip.
 //
 //   prep_det_world_kernel            one thread per detection: its image, its world position
+//   prep_det_unit_kernel, prep_match_angular_kernel
+//                                    the same join by angular distance, when an image is TAN (celeste_prep.h)
 //   prep_match_kernel                per image, one thread per detection: the nearest joined entry, the joined list through
 //                                    LDS in tiles; the list's length is read from device memory
 //   prep_append_kernel               per image, one workgroup: the unmatched detections go to the end of the list in object
@@ -63,8 +65,55 @@ __global__ void __launch_bounds__(PREP_BLOCK) prep_match_kernel(const double2 *w
     if (live) jidx[first + i] = (bi >= 0 && best < match_radius) ? bi : -1;
 }
 
-// one workgroup: the detections of the image with jidx < 0 are appended in object order
-__global__ void __launch_bounds__(PREP_BLOCK) prep_append_kernel(const double2 *world, int64_t first, int n, double2 *jpos, int32_t *jcount, int32_t *jidx) {
+struct PrepUnit { double x, y, z; };      // (cos dec cos ra, cos dec sin ra, sin dec)
+
+// one thread per detection (launched when an image is TAN): the unit vector of its world position, (ra, dec) in degrees
+__global__ void __launch_bounds__(PREP_BLOCK) prep_det_unit_kernel(const double2 *world, int64_t D, PrepUnit *unit) {
+    const int64_t d = (int64_t)blockIdx.x * PREP_BLOCK + threadIdx.x;
+    if (d >= D) return;
+    double sl, cl, sb, cb;
+    sincos(world[d].x * PREP_D2R, &sl, &cl);
+    sincos(world[d].y * PREP_D2R, &sb, &cb);
+    PrepUnit u;
+    u.x = cb * cl; u.y = cb * sl; u.z = sb;
+    unit[d] = u;
+}
+
+// prep_match_kernel with the angular distance: the chord between unit vectors orders the entries (strict <: the lowest index
+// among equal chords); the nearest is joined when 2 asind(chord / 2) < match_radius, in degrees
+__global__ void __launch_bounds__(PREP_BLOCK) prep_match_angular_kernel(const PrepUnit *unit, int64_t first, int n, const PrepUnit *junit,
+                                                                        const int32_t *jcount, double match_radius, int32_t *jidx) {
+    __shared__ PrepUnit tile[PREP_TILE];
+    const int i = blockIdx.x * PREP_BLOCK + threadIdx.x;
+    const bool live = i < n;
+    PrepUnit w;
+    w.x = 0.0; w.y = 0.0; w.z = 0.0;
+    if (live) w = unit[first + i];
+    const int cnt = *jcount;                       // (uniform over the grid)
+    double best = INFINITY;
+    int bi = -1;
+    for (int t0 = 0; t0 < cnt; t0 += PREP_TILE) {
+        const int m = min(PREP_TILE, cnt - t0);
+        for (int k = threadIdx.x; k < m; k += PREP_BLOCK) tile[k] = junit[t0 + k];
+        __syncthreads();
+        if (live)
+            for (int k = 0; k < m; ++k) {
+                const double ex = tile[k].x - w.x, ey = tile[k].y - w.y, ez = tile[k].z - w.z;
+                const double d = sqrt((ex * ex + ey * ey) + ez * ez);
+                if (d < best) { best = d; bi = t0 + k; }
+            }
+        __syncthreads();
+    }
+    if (live) {
+        const double h = best / 2.0;
+        const double sep = 2.0 * (asin(h < 1.0 ? h : 1.0) * PREP_R2D);
+        jidx[first + i] = (bi >= 0 && sep < match_radius) ? bi : -1;
+    }
+}
+
+// one workgroup: the detections of the image with jidx < 0 are appended in object order (their unit vectors too, when given)
+__global__ void __launch_bounds__(PREP_BLOCK) prep_append_kernel(const double2 *world, int64_t first, int n, double2 *jpos, int32_t *jcount, int32_t *jidx,
+                                                                 const PrepUnit *unit, PrepUnit *junit) {
     typedef hipcub::BlockScan<int, PREP_BLOCK> Scan;
     __shared__ typename Scan::TempStorage tmp;
     const int base = *jcount;
@@ -79,6 +128,7 @@ __global__ void __launch_bounds__(PREP_BLOCK) prep_append_kernel(const double2 *
             const int k = base + run + ex;
             jidx[first + i] = k;
             jpos[k] = world[first + i];
+            if (unit) junit[k] = unit[first + i];
         }
         run += tot;
     }
@@ -149,6 +199,9 @@ __global__ void __launch_bounds__(PREP_BLOCK) prep_detected_geometry_kernel(cons
     const double2 pos = jpos[s];
     double pc1, pc2;
     world_to_pix(im, pos.x, pos.y, pc1, pc2);
+    if (im.kind == CELESTE_PREP_WCS_TAN && !(fabs(pc1) < INFINITY && fabs(pc2) < INFINITY)) {   // behind the plane: the empty box
+        keep[p] = dense ? 1 : 0; pbox[p] = make_int4(1, 0, 1, 0); return;
+    }
     if (!(pc1 == pc1) || !(pc2 == pc2)) { err[0] = 1; keep[p] = 0; pbox[p] = make_int4(1, 0, 1, 0); return; }
     int32_t r0 = round_even(pc1 - min_radius), r1 = round_even(pc1 + min_radius);
     int32_t c0 = round_even(pc2 - min_radius), c1 = round_even(pc2 + min_radius);
@@ -232,6 +285,9 @@ extern "C" int celeste_prep_detected(celeste_prep_images_t *handle, const int64_
     // ---- world positions, join, the detections by joined index
     int64_t *d_off, *d_ooff = nullptr; celeste_prep_detection_t *d_det; double *d_angle; double2 *d_world, *d_jpos;
     int32_t *d_dimg, *d_didx, *d_jidx, *d_jcount, *d_sdet; uint32_t *d_skey;
+    const bool angular = handle->any_tan != 0;
+    PrepUnit *d_unit = nullptr, *d_junit = nullptr;
+    if (angular && ((st = call.alloc(&d_unit, (size_t)D)) || (st = call.alloc(&d_junit, (size_t)D)))) return st;
     if ((st = call.alloc(&d_off, (size_t)N + 1)) || (st = call.alloc(&d_det, (size_t)D)) || (st = call.alloc(&d_angle, (size_t)N)) ||
         (st = call.alloc(&d_world, (size_t)D)) || (st = call.alloc(&d_jpos, (size_t)D)) || (st = call.alloc(&d_dimg, (size_t)D)) ||
         (st = call.alloc(&d_didx, (size_t)D)) || (st = call.alloc(&d_jidx, (size_t)D)) || (st = call.alloc(&d_jcount, 1)) ||
@@ -247,14 +303,23 @@ extern "C" int celeste_prep_detected(celeste_prep_images_t *handle, const int64_
         hipLaunchKernelGGL(prep_det_world_kernel, dim3(blocks_for(D)), dim3(PREP_BLOCK), 0, q, handle->d_imgs, N, d_off, d_det, D, d_world,
                            d_dimg, d_didx);
         PREP_HIP(hipGetLastError());
+        if (angular) {
+            hipLaunchKernelGGL(prep_det_unit_kernel, dim3(blocks_for(D)), dim3(PREP_BLOCK), 0, q, d_world, D, d_unit);
+            PREP_HIP(hipGetLastError());
+        }
         for (int n = 0; n < N; ++n) {
             const int64_t first = det_offsets[n];
             const int cnt = (int)(det_offsets[n + 1] - first);
             if (cnt == 0) continue;
-            hipLaunchKernelGGL(prep_match_kernel, dim3(blocks_for(cnt)), dim3(PREP_BLOCK), 0, q, d_world, first, cnt, d_jpos, d_jcount,
-                               match_radius, d_jidx);
+            if (angular)
+                hipLaunchKernelGGL(prep_match_angular_kernel, dim3(blocks_for(cnt)), dim3(PREP_BLOCK), 0, q, d_unit, first, cnt, d_junit, d_jcount,
+                                   match_radius, d_jidx);
+            else
+                hipLaunchKernelGGL(prep_match_kernel, dim3(blocks_for(cnt)), dim3(PREP_BLOCK), 0, q, d_world, first, cnt, d_jpos, d_jcount,
+                                   match_radius, d_jidx);
             PREP_HIP(hipGetLastError());
-            hipLaunchKernelGGL(prep_append_kernel, dim3(1), dim3(PREP_BLOCK), 0, q, d_world, first, cnt, d_jpos, d_jcount, d_jidx);
+            hipLaunchKernelGGL(prep_append_kernel, dim3(1), dim3(PREP_BLOCK), 0, q, d_world, first, cnt, d_jpos, d_jcount, d_jidx,
+                               (const PrepUnit *)d_unit, d_junit);
             PREP_HIP(hipGetLastError());
         }
         const int end_bit = bits_for((uint64_t)D);

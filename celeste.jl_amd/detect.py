@@ -225,13 +225,33 @@ def world_coords(cat: Catalog, img: Image) -> np.ndarray:
     if len(cat) == 0:
         return np.zeros((0, 2))
     pix = np.stack([cat.x, cat.y], axis=1)
+    if img.wcs is not None:
+        return img.pix_to_world(pix)
     return np.linalg.solve(np.asarray(img.wcs_jacobian, float), (pix - img.wcs_pix0).T).T + img.wcs_world0
 
 
-def match_detections(worlds: Sequence[np.ndarray], match_radius: float):
+def angular_separation(lon1, lat1, lon2, lat2):
+    """Coordinates.jl:15-26: the angle in degrees between two points of the sphere, longitudes and latitudes in degrees."""
+    dl = np.radians(np.asarray(lon2, dtype=np.float64) - lon1)
+    p1, p2 = np.radians(lat1), np.radians(lat2)
+    s1, s2, c1, c2 = np.sin(p1), np.sin(p2), np.cos(p1), np.cos(p2)
+    return np.degrees(np.arctan2(np.hypot(c2 * np.sin(dl), c1 * s2 - s1 * c2 * np.cos(dl)), s1 * s2 + c1 * c2 * np.cos(dl)))
+
+
+def unit_vectors(world) -> np.ndarray:
+    """_spherical_to_cartesian (Coordinates.jl:33-45): [n, 2] (lon, lat) in degrees -> [n, 3]"""
+    w = np.radians(np.asarray(world, dtype=np.float64).reshape(-1, 2))
+    cl = np.cos(w[:, 1])
+    return np.stack([cl * np.cos(w[:, 0]), cl * np.sin(w[:, 0]), np.sin(w[:, 1])], axis=1)
+
+
+def match_detections(worlds: Sequence[np.ndarray], match_radius: float, angular: bool = False):
     """detection.jl:67-98: the joined list starts as image 1's detections; each detection of a later image joins its
     nearest joined entry (as the list stood before that image) when closer than match_radius, else it is appended.
-    Distances are planar in world coordinates (model.Image has an affine WCS; match_coordinates is angular).
+    angular=False: distances are planar in world coordinates (the affine WCS of model.Image).  angular=True: world
+    coordinates are (ra, dec) in degrees and match_radius is in degrees, as in match_coordinates (Coordinates.jl:71-86):
+    the nearest entry is the one with the shortest chord between unit vectors (the lowest index on a tie), and a
+    detection joins it when 2 asind(chord / 2) < match_radius.
     Returns (joined positions, detections: one list of (image, object) per joined entry, 0-based)."""
     if len(worlds) == 0:
         return np.zeros((0, 2)), []
@@ -242,10 +262,18 @@ def match_detections(worlds: Sequence[np.ndarray], match_radius: float):
         if w.shape[0] == 0:
             continue
         ref = np.array(joined) if joined else np.zeros((0, 2))
+        if angular:
+            uref, uw = unit_vectors(ref), unit_vectors(w)
         for j in range(w.shape[0]):
             if ref.shape[0] > 0:
-                d = np.hypot(ref[:, 0] - w[j, 0], ref[:, 1] - w[j, 1])
-                k = int(np.argmin(d))
+                if angular:
+                    e = uref - uw[j]
+                    chord = np.sqrt((e[:, 0] * e[:, 0] + e[:, 1] * e[:, 1]) + e[:, 2] * e[:, 2])
+                    k = int(np.argmin(chord))
+                    d = 2.0 * np.degrees(np.arcsin(np.minimum(chord / 2.0, 1.0)))
+                else:
+                    d = np.hypot(ref[:, 0] - w[j, 0], ref[:, 1] - w[j, 1])
+                    k = int(np.argmin(d))
                 if d[k] < match_radius:
                     detections[k].append((i, j))
                     continue
@@ -281,9 +309,10 @@ def detection_box(cat: Catalog, c: int, img: Image, world_center):
 
 
 def build_detection_output(images, catalogs: Sequence[Catalog], match_radius: float):
-    """detection.jl:61-171 given the per-image catalogs: (catalog entries, patches)."""
+    """detection.jl:61-171 given the per-image catalogs: (catalog entries, patches).  When any image has a TanWCS the join
+    is angular and match_radius is in degrees (detection.jl:87 uses 1 / 3600); affine images keep the planar distance."""
     worlds = [world_coords(cat, img) for cat, img in zip(catalogs, images)]
-    joined, detections = match_detections(worlds, match_radius)
+    joined, detections = match_detections(worlds, match_radius, angular=any(img.wcs is not None for img in images))
     x_vs_n = [x_vs_n_angle(img.wcs_jacobian) for img in images]
     sparse = len(images) > 8
     catalog, patches = [], []

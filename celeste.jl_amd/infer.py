@@ -196,6 +196,8 @@ def bad_sky(ce, images) -> bool:
     if img is None:
         return False
     pc = img.world_to_pix(ce.pos)
+    if img.wcs is not None and not np.isfinite(pc).all():
+        return False           # behind the tangent plane: the empty box
     h = max(1, min(julia_round(pc[0]), img.H))
     w = max(1, min(julia_round(pc[1]), img.W))
     claimed_sky = float(img.sky[h - 1, w - 1]) * float(img.nelec_per_nmgy[h - 1])
@@ -233,7 +235,9 @@ def bad_sky_flags(entries, images, device=None, force_torch: bool = False) -> Li
     dev = torch.device("cuda", device or 0) if torch.cuda.is_available() else torch.device("cpu")
     H, W = img.H, img.W
     pos = np.array([ce.pos for ce in entries], dtype=np.float64).reshape(-1, 2)
-    pc = (pos - img.wcs_world0) @ np.asarray(img.wcs_jacobian).T + img.wcs_pix0          # world_to_pix, row by row
+    pc = img.world_to_pix(pos)                                                           # row by row
+    if img.wcs is not None:
+        pc = np.where(np.isfinite(pc).all(axis=1)[:, None], pc, -1.0e9)                  # behind the tangent plane: the empty box
     hc = np.clip(np.rint(pc[:, 0]).astype(np.int64), 1, H)
     wc = np.clip(np.rint(pc[:, 1]).astype(np.int64), 1, W)
     claimed = img.sky[hc - 1, wc - 1].astype(np.float64) * np.asarray(img.nelec_per_nmgy)[hc - 1].astype(np.float64)

@@ -148,8 +148,16 @@ def location_box(wcs_jacobian, wcs_world0, wcs_pix0, pos0, pos_pixel_delta=(2.0,
     return np.array([ra[0], ra[1], dec[0], dec[1]])
 
 
-def image_location_box(img, pos0) -> np.ndarray:
-    return location_box(img.wcs_jacobian, img.wcs_world0, img.wcs_pix0, pos0)
+def image_location_box(img, pos0, pos_pixel_delta=(2.0, 2.0)) -> np.ndarray:
+    """location_box through the image's own WCS (make_location_prior maps its corners with the image's wcs)"""
+    if img.wcs is None:
+        return location_box(img.wcs_jacobian, img.wcs_world0, img.wcs_pix0, pos0, pos_pixel_delta)
+    pix = img.world_to_pix(np.asarray(pos0, dtype=np.float64))
+    half = 0.5 * np.asarray(pos_pixel_delta, dtype=np.float64)
+    lo, hi = img.pix_to_world(pix - half), img.pix_to_world(pix + half)
+    ra = sorted([lo[0], hi[0]])
+    dec = sorted([lo[1], hi[1]])
+    return np.array([ra[0], ra[1], dec[0], dec[1]])
 
 
 def samples_to_rows(chain: np.ndarray, is_star: bool) -> Dict[str, np.ndarray]:

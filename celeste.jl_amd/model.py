@@ -6,13 +6,13 @@ never per elbo() call) and mirrors, name for name, the reference's
   src/model/psf_model.jl:17-75         PsfComponent, get_psf_width, render_psf, ConstantPSFMap
   src/model/imaged_sources.jl:10-244   boxes, ImagePatch, box_from_catalog, get_sky_patches,
                                        choose_patch_radius, find_neighbors
-  src/model/wcs_utils.jl:14-18         linear_world_to_pix
-Only linear (affine) WCS is supported: the synthetic configurations use the
-identity WCS of test/SampleData.jl:30-34.
+  src/model/wcs_utils.jl:14-51         linear_world_to_pix, pixel_world_jacobian
+An image has an affine WCS (the identity WCS of test/SampleData.jl:30-34 in the synthetic configurations) or, with
+`Image.wcs` set, a tangent-plane (TAN) one: `TanWCS`, DESIGN.md section 16.
 """
 import collections.abc
 from dataclasses import dataclass, field
-from typing import Dict, List, Sequence, Tuple
+from typing import Dict, List, Optional, Sequence, Tuple
 import math
 import numpy as np
 
@@ -140,6 +140,89 @@ class SDSSBackground:
                               self.calibration[i - 1:i]).materialize()[0, 0]
 
 
+class TanWCS:
+    """The gnomonic (TAN) projection of FITS WCS paper II (Calabretta & Greisen 2002, section 5.1.3) behind a CD matrix,
+    in fp64.  crval = (ra0, dec0) in degrees; crpix = the 1-based reference pixel in (h, w) order (FITS axis 1 = h);
+    cd = 2 x 2 degrees per pixel, cd[0, 1] = CD1_2.  With da = ra - ra0:
+        l = cos(dec) sin(da);  m = sin(dec) cos(dec0) - cos(dec) sin(dec0) cos(da);  n = sin(dec) sin(dec0) + cos(dec) cos(dec0) cos(da)
+        (m is evaluated as sin(dec - dec0) + 2 cos(dec) sin(dec0) sin^2(da / 2), the same number without the cancellation)
+        (x, y) = (180 / pi) (l, m) / n;  pix = crpix + cd^-1 (x, y)
+    No SIP or other distortion terms.  All methods are vectorised over [..., 2]."""
+
+    def __init__(self, crval, crpix, cd):
+        self.crval = np.array(crval, dtype=np.float64).reshape(2)
+        self.crpix = np.array(crpix, dtype=np.float64).reshape(2)
+        self.cd = np.array(cd, dtype=np.float64).reshape(2, 2)
+        if not (np.isfinite(self.crval).all() and np.isfinite(self.crpix).all() and np.isfinite(self.cd).all()):
+            raise ValueError("TanWCS: non-finite field")
+        if abs(self.crval[1]) > 90.0:
+            raise ValueError("TanWCS: |dec0| > 90")
+        det = self.cd[0, 0] * self.cd[1, 1] - self.cd[0, 1] * self.cd[1, 0]
+        if det == 0.0:
+            raise ValueError("TanWCS: singular cd")
+        # cd^-1 by the adjugate, the four quotients the device library forms too
+        self.cdinv = np.array([[self.cd[1, 1] / det, -self.cd[0, 1] / det], [-self.cd[1, 0] / det, self.cd[0, 0] / det]])
+        d0 = math.radians(self.crval[1])
+        self._sin0, self._cos0 = math.sin(d0), math.cos(d0)
+        for a in (self.crval, self.crpix, self.cd, self.cdinv):
+            a.setflags(write=False)
+
+    def __repr__(self):
+        return "TanWCS(crval=%r, crpix=%r, cd=%r)" % (self.crval.tolist(), self.crpix.tolist(), self.cd.tolist())
+
+    def world_to_pix(self, world):
+        """(ra, dec) in degrees -> 1-based (h, w); NaN behind the tangent plane (n <= 0).  Any RA branch: only sin and cos
+        of ra - ra0 are used."""
+        world = np.asarray(world, dtype=np.float64)
+        da = np.radians(world[..., 0] - self.crval[0])
+        dec = np.radians(world[..., 1])
+        sd, cdec, sa, ca = np.sin(dec), np.cos(dec), np.sin(da), np.cos(da)
+        l = cdec * sa
+        # m = sin(dec) cos(dec0) - cos(dec) sin(dec0) cos(da) without its cancellation near the tangent point:
+        # sin(dec - dec0) + 2 cos(dec) sin(dec0) sin^2(da / 2)
+        sh = np.sin(0.5 * da)
+        m = np.sin(np.radians(world[..., 1] - self.crval[1])) + (2.0 * (cdec * self._sin0)) * (sh * sh)
+        n = sd * self._sin0 + (cdec * self._cos0) * ca
+        with np.errstate(divide="ignore", invalid="ignore"):
+            x = np.degrees(l / n)
+            y = np.degrees(m / n)
+        ci = self.cdinv
+        out = np.stack([self.crpix[0] + (ci[0, 0] * x + ci[0, 1] * y), self.crpix[1] + (ci[1, 0] * x + ci[1, 1] * y)], axis=-1)
+        behind = ~(n > 0.0)
+        if behind.any():
+            out = np.where(behind[..., None], np.nan, out)
+        return out
+
+    def pix_to_world(self, pix):
+        """1-based (h, w) -> (ra, dec) in degrees; ra is continuous around crval[0] (within 180 degrees of it), not
+        wrapped into [0, 360)."""
+        pix = np.asarray(pix, dtype=np.float64)
+        u, v = pix[..., 0] - self.crpix[0], pix[..., 1] - self.crpix[1]
+        x = np.radians(self.cd[0, 0] * u + self.cd[0, 1] * v)
+        y = np.radians(self.cd[1, 0] * u + self.cd[1, 1] * v)
+        den = self._cos0 - y * self._sin0
+        num = self._sin0 + y * self._cos0
+        ra = self.crval[0] + np.degrees(np.arctan2(x, den))
+        # (sin dec, cos dec) = (num, hyp) / |.|; dec - dec0 = atan2(num cos0 - hyp sin0, num sin0 + hyp cos0), whose first
+        # argument is y - sin0 (hyp - den) = y - sin0 x^2 / (hyp + den) without cancellation: crpix -> crval exactly
+        hyp = np.hypot(x, den)
+        dec = self.crval[1] + np.degrees(np.arctan2(y - self._sin0 * ((x * x) / (hyp + den)), num * self._sin0 + hyp * self._cos0))
+        return np.stack([ra, dec], axis=-1)
+
+    def jacobian(self, pix, pixel_delt: float = 0.5):
+        """pixel_world_jacobian (wcs_utils.jl:36-51), step rule and all: a finite difference in raw (ra, dec) whose step is
+        the larger coordinate change over (pixel_delt, pixel_delt) pixels.  [..., 2, 2], d pix / d world."""
+        pix = np.asarray(pix, dtype=np.float64)
+        world = self.pix_to_world(pix)
+        delt = np.abs(self.pix_to_world(pix + pixel_delt) - world).max(axis=-1)
+        w1, w2 = world.copy(), world.copy()
+        w1[..., 0] += delt
+        w2[..., 1] += delt
+        c1 = (self.world_to_pix(w1) - pix) / delt[..., None]
+        c2 = (self.world_to_pix(w2) - pix) / delt[..., None]
+        return np.stack([c1, c2], axis=-1)
+
+
 @dataclass
 class Image:
     """image_model.jl:6-38.  pixels/sky are H x W (first index = row h), float32."""
@@ -152,6 +235,7 @@ class Image:
     wcs_jacobian: np.ndarray = field(default_factory=lambda: np.eye(2))  # affine WCS: pix = J (world - w0) + p0
     wcs_world0: np.ndarray = field(default_factory=lambda: np.zeros(2))
     wcs_pix0: np.ndarray = field(default_factory=lambda: np.zeros(2))
+    wcs: Optional[TanWCS] = None  # a tangent-plane WCS (with_tan_wcs); None: the affine one above
 
     @property
     def H(self):
@@ -162,10 +246,44 @@ class Image:
         return self.pixels.shape[1]
 
     def world_to_pix(self, world):
-        return self.wcs_jacobian @ (np.asarray(world, float) - self.wcs_world0) + self.wcs_pix0
+        """[..., 2] world -> pixel"""
+        world = np.asarray(world, float)
+        if self.wcs is not None:
+            return self.wcs.world_to_pix(world)
+        if world.ndim == 1:
+            return self.wcs_jacobian @ (world - self.wcs_world0) + self.wcs_pix0
+        return (world - self.wcs_world0) @ self.wcs_jacobian.T + self.wcs_pix0
 
     def pix_to_world(self, pix):
-        return np.linalg.solve(self.wcs_jacobian, np.asarray(pix, float) - self.wcs_pix0) + self.wcs_world0
+        """[..., 2] pixel -> world (affine: one LAPACK solve per position)"""
+        pix = np.asarray(pix, float)
+        if self.wcs is not None:
+            return self.wcs.pix_to_world(pix)
+        if pix.ndim == 1:
+            return np.linalg.solve(self.wcs_jacobian, pix - self.wcs_pix0) + self.wcs_world0
+        rhs = (pix - self.wcs_pix0)[..., None]
+        return np.linalg.solve(np.broadcast_to(self.wcs_jacobian, pix.shape[:-1] + (2, 2)), rhs)[..., 0] + self.wcs_world0
+
+    def jacobian_at(self, pix):
+        """d pix / d world at `pix`: the reference's pixel_world_jacobian for a TanWCS, the constant matrix otherwise"""
+        if self.wcs is not None:
+            return self.wcs.jacobian(pix)
+        pix = np.asarray(pix, float)
+        if pix.ndim == 1:
+            return self.wcs_jacobian.copy()
+        return np.broadcast_to(self.wcs_jacobian, pix.shape[:-1] + (2, 2)).copy()
+
+
+def with_tan_wcs(img: Image, wcs: TanWCS) -> Image:
+    """`img` with the tangent-plane WCS `wcs`; the affine fields take its linearisation at crpix (inv(cd), crval, crpix), so
+    detect.x_vs_n_angle(img.wcs_jacobian) is the reference's _x_vs_n_angle of the CD matrix."""
+    img.wcs = wcs
+    img.wcs_jacobian = np.array(wcs.cdinv)
+    img.wcs_world0 = np.array(wcs.crval)
+    img.wcs_pix0 = np.array(wcs.crpix)
+    if hasattr(img, "_empty_patch"):
+        del img._empty_patch
+    return img
 
 
 Box = Tuple[Tuple[int, int], Tuple[int, int]]  # ((first, last), (first, last)), inclusive, 1-based
@@ -212,7 +330,7 @@ class ImagePatch:
         sub = img.pixels[off[0]:off[0] + h2, off[1]:off[1] + w2]
         bitmap = ~np.isnan(sub)
         return cls(box, world_center, img.psf, img.psfmap(pixel_center[0], pixel_center[1]),
-                   img.wcs_jacobian.copy(), pixel_center, off, bitmap, stamp_id)
+                   img.jacobian_at(pixel_center), pixel_center, off, bitmap, stamp_id)
 
 
 def empty_patch(img: Image) -> ImagePatch:
@@ -221,7 +339,7 @@ def empty_patch(img: Image) -> ImagePatch:
     p = getattr(img, "_empty_patch", None)
     if p is None:
         p = ImagePatch(((1, 0), (1, 0)), img.pix_to_world(np.array([0.5, 0.5])), img.psf, img.psfmap(0.5, 0.5),
-                       img.wcs_jacobian.copy(), np.array([0.5, 0.5]), (0, 0), np.zeros((0, 0), dtype=bool))
+                       img.jacobian_at(np.array([0.5, 0.5])), np.array([0.5, 0.5]), (0, 0), np.zeros((0, 0), dtype=bool))
         img._empty_patch = p
     return p
 
@@ -265,6 +383,8 @@ def row_entries(row):
 def box_around_point(img: Image, world_center, pixel_radius: float) -> Box:
     """imaged_sources.jl:120-136"""
     pc = img.world_to_pix(world_center)
+    if img.wcs is not None and not (np.isfinite(pc[0]) and np.isfinite(pc[1])):
+        return ((1, 0), (1, 0))    # behind the tangent plane: the empty box
     return ((julia_round(pc[0] - pixel_radius), julia_round(pc[0] + pixel_radius)),
             (julia_round(pc[1] - pixel_radius), julia_round(pc[1] + pixel_radius)))
 
@@ -317,7 +437,7 @@ def get_sky_patches(images: Sequence[Image], catalog: Sequence[CatalogEntry],
     pos = np.array([ce.pos for ce in catalog], dtype=float).reshape(-1, 2)
     entries = [dict() for _ in catalog]
     for n, img in enumerate(images):
-        pc = (pos - img.wcs_world0) @ img.wcs_jacobian.T + img.wcs_pix0
+        pc = img.world_to_pix(pos)
         near = np.flatnonzero((pc[:, 0] > -reach) & (pc[:, 0] < img.H + 1 + reach) &
                               (pc[:, 1] > -reach) & (pc[:, 1] < img.W + 1 + reach))
         for s in near:
@@ -342,6 +462,7 @@ class PatchTable:
     pixel_center: np.ndarray  # [E, 2]
     world_center: np.ndarray  # [E, 2]
     active_pixels: np.ndarray  # [E] int64: pixels of the box that are not NaN (ParallelRun.jl:45-47's cost)
+    wcs_jacobian: Optional[np.ndarray] = None  # [E, 2, 2]: per-patch Jacobians, when some image has a TanWCS (else the image's)
 
     @property
     def H2(self):
@@ -404,7 +525,7 @@ def patch_table(images: Sequence[Image], catalog: Sequence[CatalogEntry], radius
     pos = np.array([ce.pos for ce in catalog], dtype=float).reshape(-1, 2)
     for n, img in enumerate(images):
         if sparse:
-            pc = (pos - img.wcs_world0) @ img.wcs_jacobian.T + img.wcs_pix0
+            pc = img.world_to_pix(pos)
             cand = np.flatnonzero((pc[:, 0] > -reach) & (pc[:, 0] < img.H + 1 + reach) &
                                   (pc[:, 1] > -reach) & (pc[:, 1] < img.W + 1 + reach)).tolist()
         else:
@@ -426,15 +547,16 @@ def patch_table(images: Sequence[Image], catalog: Sequence[CatalogEntry], radius
     source, image, box = source[order], image[order], box[order]
     pixel_center = np.stack([(box[:, 0] + box[:, 1]) / 2, (box[:, 2] + box[:, 3]) / 2], axis=1)
     world_center = np.zeros_like(pixel_center)
+    jac = np.zeros((len(source), 2, 2)) if any(im.wcs is not None for im in images) else None
     active = np.zeros(len(source), dtype=np.int64)
     h2 = np.maximum(box[:, 1] - box[:, 0] + 1, 0); w2 = np.maximum(box[:, 3] - box[:, 2] + 1, 0)
     for n, img in enumerate(images):
         e = np.flatnonzero(image == n)
         if e.size == 0:
             continue
-        # pix_to_world, one LAPACK solve per centre exactly as Image.pix_to_world does it
-        rhs = (pixel_center[e] - img.wcs_pix0)[:, :, None]
-        world_center[e] = np.linalg.solve(np.broadcast_to(img.wcs_jacobian, (e.size, 2, 2)), rhs)[:, :, 0] + img.wcs_world0
+        world_center[e] = img.pix_to_world(pixel_center[e])
+        if jac is not None:
+            jac[e] = img.jacobian_at(pixel_center[e])
         nan = np.isnan(img.pixels)
         if not nan.any():
             active[e] = h2[e] * w2[e]
@@ -444,7 +566,7 @@ def patch_table(images: Sequence[Image], catalog: Sequence[CatalogEntry], radius
             r0, r1 = box[e, 0] - 1, np.maximum(box[e, 1], box[e, 0] - 1)
             c0, c1 = box[e, 2] - 1, np.maximum(box[e, 3], box[e, 2] - 1)
             active[e] = np.where((h2[e] > 0) & (w2[e] > 0), sat[r1, c1] - sat[r0, c1] - sat[r1, c0] + sat[r0, c0], 0)
-    return PatchTable(S, N, not sparse, source, image, box, pixel_center, world_center, active)
+    return PatchTable(S, N, not sparse, source, image, box, pixel_center, world_center, active, jac)
 
 
 def table_for(images, catalog, sparse: bool, prep_device=None, prep_images=None) -> PatchTable:

@@ -7,10 +7,11 @@
   SDSSPSFMap.__call__ at every patch centre                  table.stamp / table.stamps (the same call)
   infer.bad_sky per catalog entry                            bad_sky_flags        (celeste_prep_bad_sky)
   detect.build_detection_output + model.neighbor_map         detected_table       (celeste_prep_detected)
+  model.TanWCS of an image (projection, patch Jacobians)     PrepImages           (celeste_prep_images_set_wcs)
 
 `PrepImages` uploads the planes once (numpy's row-major H x W arrays as they are) and serves any number of calls;
 patch_table and bad_sky_flags make one of their own when none is given.  include/celeste_prep.h and DESIGN.md section 14
-state the arithmetic: boxes, centres, counts, neighbour lists and flags are the host functions', exactly; the stamps and a
+and 16 state the arithmetic: boxes, centres, counts, neighbour lists and flags are the host functions', exactly; the stamps and a
 non-trivial Jacobian's world centres agree with numpy's within rounding (their summation orders are not numpy's).
 The kernels are HIP (csrc/prep/celeste_prep.hip); there is no CPU path.
 """
@@ -30,7 +31,8 @@ ABI_VERSION = 100          # CELESTE_PREP_ABI_VERSION of include/celeste_prep.h
 EXPORTED_SYMBOLS = ["celeste_prep_version", "celeste_prep_strerror", "celeste_prep_images_create", "celeste_prep_images_destroy",
                     "celeste_prep_patches", "celeste_prep_result_get", "celeste_prep_result_destroy", "celeste_prep_bad_sky",
                     "celeste_prep_last_ms", "celeste_prep_detected_check", "celeste_prep_detected",
-                    "celeste_prep_result_get_catalog", "celeste_prep_detected_last_ms"]
+                    "celeste_prep_result_get_catalog", "celeste_prep_detected_last_ms", "celeste_prep_wcs_check",
+                    "celeste_prep_images_set_wcs", "celeste_prep_result_get_jacobians"]
 ERR_INVALID_ARG, ERR_NO_DEVICE, ERR_HIP, ERR_ALLOC = 1, 2, 3, 4
 FLAG_DENSE, FLAG_STAMPS = 1, 2
 STAMP = 51                 # CELESTE_PREP_STAMP
@@ -41,6 +43,7 @@ MATCH_BLOCK = 256          # CELESTE_PREP_MATCH_BLOCK: detections per workgroup 
 DETECTED_N_STAGES = 6      # CELESTE_PREP_DETECTED_N_STAGES
 DETECTED_STAGES = ("join", "entries", "geometry", "active_pixels", "neighbors", "stamps")
 MIN_RADIUS_PIX, DILATE = 5.0, 0.2     # detection.jl:152-167
+WCS_AFFINE, WCS_TAN = 0, 1            # celeste_prep_wcs_t.kind
 
 c_float_p, c_double_p = C.POINTER(C.c_float), C.POINTER(C.c_double)
 
@@ -54,6 +57,12 @@ class PrepImageT(C.Structure):
                 ("wcs_pix0", C.c_double * 2), ("psf_width", C.c_double), ("epsilon", C.c_double),
                 ("rnrow", C.c_int32), ("rncol", C.c_int32), ("ni", C.c_int32), ("nj", C.c_int32), ("nk", C.c_int32),
                 ("reserved2", C.c_int32), ("rrows", c_double_p), ("cmat", c_double_p)]
+
+
+class PrepWcsT(C.Structure):
+    """celeste_prep_wcs_t"""
+    _fields_ = [("kind", C.c_int32), ("reserved", C.c_int32), ("crval", C.c_double * 2), ("crpix", C.c_double * 2),
+                ("cd", C.c_double * 4)]
 
 
 class PrepSourceT(C.Structure):
@@ -144,6 +153,12 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.celeste_prep_result_get_catalog.argtypes = [vp, C.POINTER(PrepCatalogT)]
     lib.celeste_prep_detected_last_ms.restype = C.c_int
     lib.celeste_prep_detected_last_ms.argtypes = [c_float_p]
+    lib.celeste_prep_wcs_check.restype = C.c_int
+    lib.celeste_prep_wcs_check.argtypes = [C.c_int32, C.POINTER(PrepWcsT)]
+    lib.celeste_prep_images_set_wcs.restype = C.c_int
+    lib.celeste_prep_images_set_wcs.argtypes = [vp, C.c_int32, C.POINTER(PrepWcsT)]
+    lib.celeste_prep_result_get_jacobians.restype = C.c_int
+    lib.celeste_prep_result_get_jacobians.argtypes = [vp, C.POINTER(c_double_p)]
     if path == LIB_PATH or path == os.environ.get("CELESTE_MI355X_PREP_LIB"):
         _lib = lib
     return lib
@@ -215,6 +230,22 @@ def image_structs(images, keep: list):
     return arr
 
 
+def wcs_structs(images):
+    """Model.Image list -> celeste_prep_wcs_t array: kind TAN for an image with a model.TanWCS, else AFFINE"""
+    arr = (PrepWcsT * max(len(images), 1))()
+    for n, im in enumerate(images):
+        w = getattr(im, "wcs", None)
+        if w is None:
+            arr[n].kind = WCS_AFFINE
+            continue
+        arr[n].kind = WCS_TAN
+        arr[n].crval[0], arr[n].crval[1] = float(w.crval[0]), float(w.crval[1])
+        arr[n].crpix[0], arr[n].crpix[1] = float(w.crpix[0]), float(w.crpix[1])
+        arr[n].cd[0], arr[n].cd[1], arr[n].cd[2], arr[n].cd[3] = (float(w.cd[0, 0]), float(w.cd[0, 1]), float(w.cd[1, 0]),
+                                                                  float(w.cd[1, 1]))
+    return arr
+
+
 class PrepImages:
     """celeste_prep_images_t: the planes, calibrations, WCS and eigen-PSFs of `images` on `device`.  A context manager;
     `close()` releases the device memory."""
@@ -229,6 +260,13 @@ class PrepImages:
         h = C.c_void_p()
         _check(self.lib, self.lib.celeste_prep_images_create(self.device, len(images), arr, C.byref(h)))
         self.handle = h
+        self.has_tan_wcs = any(getattr(im, "wcs", None) is not None for im in images)
+        if self.has_tan_wcs:
+            self.set_wcs(wcs_structs(images))
+
+    def set_wcs(self, arr, n: Optional[int] = None):
+        """celeste_prep_images_set_wcs with a celeste_prep_wcs_t array (wcs_structs)"""
+        _check(self.lib, self.lib.celeste_prep_images_set_wcs(self.handle, len(self.images) if n is None else n, arr))
 
     def close(self):
         if getattr(self, "handle", None):
@@ -316,6 +354,11 @@ def _table_from_result(lib, rh, res, n_images: int, sparse: bool, with_stamps: b
     off = _view(t.nbr_offsets, (S + 1,), np.int64).tolist()
     idx = _view(t.nbr_index, (int(t.n_neighbors),), np.int32).tolist()
     table.neighbor_lists = [idx[off[s]:off[s + 1]] for s in range(S)]
+    jp = c_double_p()
+    _check(lib, lib.celeste_prep_result_get_jacobians(rh, C.byref(jp)))
+    if jp:       # some image has a TanWCS: per-patch Jacobians, [E][4] = J11, J21, J12, J22
+        j = _view(jp, (E, 4), np.float64)
+        table.wcs_jacobian = np.stack([j[:, 0], j[:, 2], j[:, 1], j[:, 3]], axis=1).reshape(E, 2, 2)
     if with_stamps:
         table.stamp = _view(t.stamp, (E,), np.int32).copy()
         table.stamps = _view(t.stamps, (int(t.n_stamps), STAMP * STAMP), np.float64)   # a view: no copy of the stamps

@@ -124,6 +124,9 @@ def entry_table(images, catalog):
         d0, d1 = pos[:, 0] - w0[0], pos[:, 1] - w0[1]
         pc0 = J[0, 0] * d0 + J[0, 1] * d1 + p0[0]            # box_around_point: img.world_to_pix(pos)
         pc1 = J[1, 0] * d0 + J[1, 1] * d1 + p0[1]
+        if img.wcs is not None:
+            pc = img.world_to_pix(pos)
+            pc0, pc1 = pc[:, 0], pc[:, 1]
         with np.errstate(invalid="ignore"):
             far = ~((np.abs(pc0) < 2.0 ** 30) & (np.abs(pc1) < 2.0 ** 30))   # (and NaN): no box anywhere near the image
         pc0, pc1 = np.where(far, -1e9, pc0), np.where(far, -1e9, pc1)
@@ -139,12 +142,17 @@ def entry_table(images, catalog):
         # ImagePatch.from_box: pixel_center, world_center = pix_to_world(pixel_center); m = J (pos - world_center) + pixel_center
         cen = np.stack([(h0 + h1) / 2, (v0 + v1) / 2], axis=1)
         wc = np.linalg.solve(J, (cen - p0).T).T + w0
+        J00, J01, J10, J11 = J[0, 0], J[0, 1], J[1, 0], J[1, 1]
+        if img.wcs is not None:     # the patch's own centre and Jacobian
+            wc = img.pix_to_world(cen)
+            Jp = img.jacobian_at(cen)
+            J00, J01, J10, J11 = Jp[:, 0, 0], Jp[:, 0, 1], Jp[:, 1, 0], Jp[:, 1, 1]
         e0, e1 = pos[keep, 0] - wc[:, 0], pos[keep, 1] - wc[:, 1]
         ent = np.zeros(keep.size, dtype=ENTRY_DTYPE)
         ent["image"], ent["source"] = n, keep
         ent["h0"], ent["h1"], ent["w0"], ent["w1"] = h0, h1, v0, v1
-        ent["m"][:, 0] = J[0, 0] * e0 + J[0, 1] * e1 + cen[:, 0]
-        ent["m"][:, 1] = J[1, 0] * e0 + J[1, 1] * e1 + cen[:, 1]
+        ent["m"][:, 0] = J00 * e0 + J01 * e1 + cen[:, 0]
+        ent["m"][:, 1] = J10 * e0 + J11 * e1 + cen[:, 1]
         star = is_star[keep]
         ent["is_star"] = star
         ent["flux"] = np.where(star, sflux[keep, img.b - 1], gflux[keep, img.b - 1])

@@ -20,8 +20,8 @@ from typing import List, Optional
 import numpy as np
 
 from . import cabi
-from .model import (ConstantPSFMap, Image, ImagePatch, SDSSBackground, SDSSPSFMap, box_around_point, get_sky_patches,
-                    make_psf, neighbor_map, render_psf)
+from .model import (ConstantPSFMap, Image, ImagePatch, SDSSBackground, SDSSPSFMap, TanWCS, box_around_point, get_sky_patches,
+                    make_psf, neighbor_map, render_psf, with_tan_wcs)
 from .params import CatalogEntry, catalog_init_source, perturb_params
 
 SKY_NMGY = (0.20, 0.35, 0.60, 0.95, 1.40)
@@ -169,8 +169,7 @@ def render_expected_image(img: Image, catalog: List[CatalogEntry]) -> np.ndarray
     nm = img.sky.astype(np.float64).copy()
     constant_map = isinstance(img.psfmap, ConstantPSFMap)
     coef = cabi.spline_prefilter(img.psfmap(0, 0)) if constant_map else None
-    pc = (np.array([ce.pos for ce in catalog], dtype=float).reshape(-1, 2) - img.wcs_world0) @ img.wcs_jacobian.T \
-        + img.wcs_pix0
+    pc = img.world_to_pix(np.array([ce.pos for ce in catalog], dtype=float).reshape(-1, 2))
     near = np.flatnonzero((pc[:, 0] > -27) & (pc[:, 0] < img.H + 28) & (pc[:, 1] > -27) & (pc[:, 1] < img.W + 28))
     for ce in (catalog[s] for s in near):   # the others' radius-25 boxes miss the image
         box = box_around_point(img, ce.pos, 25)
@@ -285,8 +284,9 @@ class Field:
 
 def make_field(H: int, W: int, n_sources: int, seed: int, stars_only: bool = False, perturb: bool = True,
                nan_fraction: float = 0.0, margin: int = 26, name: str = "", variable: bool = False,
-               device: Optional[int] = None) -> Field:
+               device: Optional[int] = None, wcs: Optional[TanWCS] = None) -> Field:
     """Configs 2 / 3 of SURVEY.md 8(d): uniform positions with a margin, prior-drawn sources.
+    wcs (a model.TanWCS): every image gets it and the catalog positions, drawn in pixels as before, are (ra, dec) in degrees.
     variable=True: SDSS-like varying sky plane, per-row calibration and per-patch PSF stamps (`variable_images`)
     instead of the constant template of AccuracyBenchmark.make_image.
     device (an integer): the pixels come from that device, with `seed` as the Philox seed (gen_images); the catalog and the
@@ -294,9 +294,14 @@ def make_field(H: int, W: int, n_sources: int, seed: int, stars_only: bool = Fal
     rng = np.random.Generator(np.random.PCG64(seed))
     prior = load_prior()
     images = variable_images(H, W, seed) if variable else blank_images(H, W)
+    if wcs is not None:
+        for im in images:
+            with_tan_wcs(im, wcs)
     catalog = []
     for _ in range(n_sources):
         pos = (rng.uniform(margin, H - margin), rng.uniform(margin, W - margin))
+        if wcs is not None:
+            pos = wcs.pix_to_world(np.array(pos))
         catalog.append(draw_source(prior, rng, pos, force_star=True if stars_only else None))
     gen_images(images, catalog, rng, seed=seed, device=device)
     if nan_fraction > 0:
@@ -313,24 +318,49 @@ def make_field(H: int, W: int, n_sources: int, seed: int, stars_only: bool = Fal
 
 def make_multifield(grid=(2, 2), H: int = 256, W: int = 256, overlap: float = 0.10, n_sources: int = 120,
                     seed: int = 5, perturb: bool = True, margin: int = 8, sparse: bool = False,
-                    workers: int = 1, device: Optional[int] = None) -> Field:
+                    workers: int = 1, device: Optional[int] = None, wcs: Optional[str] = None, crval=(0.0, 0.0),
+                    pixel_scale_deg: float = 0.396 / 3600.0, rotations=None) -> Field:
     """Config 5 of SURVEY.md 8(d) in miniature: a grid of overlapping fields (5 bands each) on one world
     coordinate system (world = global pixel coordinates; each image has its own affine offset).  A source
     has non-empty patches only in the images it overlaps; the others are the reference's empty boxes
-    (clamp_box, imaged_sources.jl:10-14).  device: as in make_field."""
+    (clamp_box, imaged_sources.jl:10-14).  device: as in make_field.
+    wcs="tan": the global pixel grid becomes a tangent plane at crval = (ra0, dec0) (degrees) with pixel_scale_deg degrees
+    per pixel, and every field gets a TanWCS of its own: tangent at the sky position of its centre pixel, turned about it by
+    rotations[k] degrees (field k in grid order; an item (degrees, True) also flips the parity; default: no rotation).
+    Catalog positions, drawn on the global grid as before, are then (ra, dec) in degrees."""
     rng = np.random.Generator(np.random.PCG64(seed))
     prior = load_prior()
     images: List[Image] = []
     step_h, step_w = int(round(H * (1 - overlap))), int(round(W * (1 - overlap)))
+    tot_h, tot_w = step_h * (grid[0] - 1) + H, step_w * (grid[1] - 1) + W
+    if wcs not in (None, "tan"):
+        raise ValueError("wcs: None or 'tan'")
+    sky = None
+    if wcs == "tan":
+        sky = TanWCS(crval, ((tot_h + 1) / 2.0, (tot_w + 1) / 2.0), pixel_scale_deg * np.eye(2))
     for gi in range(grid[0]):
         for gj in range(grid[1]):
+            field_wcs = None
+            if sky is not None:
+                k = gi * grid[1] + gj
+                rot = rotations[k] if rotations is not None else 0.0
+                rot, flip = rot if isinstance(rot, (tuple, list)) else (rot, False)
+                t = math.radians(rot)
+                cd = pixel_scale_deg * np.array([[math.cos(t), -math.sin(t)], [math.sin(t), math.cos(t)]])
+                if flip:
+                    cd = cd @ np.diag([1.0, -1.0])
+                centre = np.array([(H + 1) / 2.0, (W + 1) / 2.0])
+                field_wcs = TanWCS(sky.pix_to_world(centre + np.array([float(gi * step_h), float(gj * step_w)])), centre, cd)
             for im in blank_images(H, W):
                 im.wcs_world0 = np.array([float(gi * step_h), float(gj * step_w)])
+                if field_wcs is not None:
+                    with_tan_wcs(im, field_wcs)
                 images.append(im)
-    tot_h, tot_w = step_h * (grid[0] - 1) + H, step_w * (grid[1] - 1) + W
     catalog = []
     for _ in range(n_sources):
         pos = (rng.uniform(margin, tot_h - margin), rng.uniform(margin, tot_w - margin))
+        if sky is not None:
+            pos = sky.pix_to_world(np.array(pos))
         catalog.append(draw_source(prior, rng, pos))
     gen_images(images, catalog, rng, workers=workers, seed=seed, device=device)
     patches = get_sky_patches(images, catalog, sparse=sparse)

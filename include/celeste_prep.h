@@ -3,7 +3,8 @@
  * What model.patch_table, PatchTable.neighbors, SDSSPSFMap.__call__ and infer.bad_sky compute on the host, one (source,
  * image) pair at a time, for a whole catalog in a fixed number of launches: the patch geometry of get_sky_patches
  * (imaged_sources.jl:120-223), the neighbour lists of find_neighbors (imaged_sources.jl:232-244), the eigen-PSF stamps of
- * SDSSIO.jl:239-299 and the sky check of ParallelRun.jl:437-460.  Only the affine WCS pix = J (world - world0) + pix0.
+ * SDSSIO.jl:239-299 and the sky check of ParallelRun.jl:437-460.  An image has the affine WCS pix = J (world - world0) + pix0
+ * or, after celeste_prep_images_set_wcs, a tangent-plane (TAN) one (below).
  *
  * All arithmetic is fp64 (the median: Float32, as the pixels are), compiled without contraction: a * b + c is a rounded
  * product and a rounded sum everywhere in this library.  No result uses a floating-point atomic; results repeat bit for
@@ -64,6 +65,31 @@
  *         holds the widened ranges and minbox.  Without one the box is minbox.  Then clamp_box.  An entry for every pair
  *         (DENSE) or for the pairs whose clamped box holds a pixel; from there on as for celeste_prep_patches.
  *
+ * Tangent-plane images (celeste_prep_wcs_t.kind = CELESTE_PREP_WCS_TAN; world = (ra, dec) in degrees): wherever the text above
+ * says world_to_pix or J^-1 (...) + world0, such an image uses the gnomonic projection of FITS WCS paper II, in fp64:
+ *     world_to_pix: da = (ra - crval1) D, dec' = dec D, D = pi / 180;  l = cos dec' sin da;
+ *         m = sin((dec - crval2) D) + (2 (cos dec' sin0)) (sh sh), sh = sin(da / 2)     [= sin dec' cos0 - cos dec' sin0 cos da, without
+ *         its cancellation near the tangent point];  n = sin dec' sin0 + (cos dec' cos0) cos da     (sin0, cos0 of crval2 D: the host's libm)
+ *         x = (l / n) / D', y = (m / n) / D' with 1 / D' = 180 / pi;  pc1 = crpix1 + (I11 x + I12 y);  pc2 = crpix2 + (I21 x + I22 y),
+ *         I = cd^-1 by the adjugate (four quotients by the determinant, formed on the host).  Not n > 0 (behind the plane): NaN.
+ *     pix_to_world: u = c1 - crpix1, v = c2 - crpix2;  x = (cd11 u + cd12 v) D;  y = (cd21 u + cd22 v) D;
+ *         den = cos0 - y sin0;  num = sin0 + y cos0;  hyp = hypot(x, den);  ra = crval1 + atan2(x, den) / D';
+ *         dec = crval2 + atan2(y - sin0 ((x x) / (hyp + den)), num sin0 + hyp cos0) / D'     [the first argument is num cos0 - hyp sin0
+ *         without cancellation; crpix maps to crval exactly]
+ *         -- ra is continuous around crval1, not wrapped into [0, 360).
+ *     Jacobian of an entry (pixel_world_jacobian, wcs_utils.jl:36-51, pixel_delt 0.5), at its pixel_center c:
+ *         w = pix_to_world(c);  t = the larger of |pix_to_world(c + (0.5, 0.5)) - w| over the two coordinates;
+ *         column 1 = (world_to_pix(w + (t, 0)) - c) / t,  column 2 = (world_to_pix(w + (0, t)) - c) / t.
+ *     A pair whose pixel coordinates are not finite (behind the plane) gets the empty box 1 .. 0 and is no error; the sky
+ *     check of such a position is 0.  sin, cos, atan2, hypot and asin are the device's (they may differ from libm in the last
+ *     places; boxes agree with the host's unless pc -/+ r lies that close to a rounding tie).
+ *     Join, when any image is TAN: every detection goes to the unit vector (cos dec' cos ra', cos dec' sin ra', sin dec');
+ *         d = sqrt((ex ex + ey ey) + ez ez) of the difference e of two unit vectors (the chord) takes the place of the planar
+ *         distance, with the same order and tie rules; the nearest entry is joined when 2 (asin(min(d / 2, 1)) / D') < match_radius,
+ *         match_radius in degrees (Coordinates.jl:71-86).  Images that are all affine keep the planar distance.
+ *     A problem's catalog and images must lie on one RA branch across 0 / 360: world_to_pix accepts any branch, but positions
+ *     returned by pix_to_world are on crval1's.
+ *
  * Thread safety: calls are serialised inside the library.  Without a HIP device the entry points that compute return
  * CELESTE_PREP_ERR_NO_DEVICE -- there is no CPU path.  Invalid arguments are refused before any HIP call (the flux and NaN
  * checks above are part of the geometry kernel and are reported when it has run). */
@@ -117,6 +143,17 @@ typedef struct celeste_prep_image_t {
     const double *rrows;             /* (rnrow rncol) x nk, row-major: rrows[p nk + k]; NULL: a constant PSF map */
     const double *cmat;              /* ni x nj x nk, row-major: cmat[(i nj + j) nk + k] */
 } celeste_prep_image_t;
+
+enum { CELESTE_PREP_WCS_AFFINE = 0, CELESTE_PREP_WCS_TAN = 1 };
+
+/* the WCS of one image: kind AFFINE keeps celeste_prep_image_t's matrix (the other fields are not read); kind TAN: */
+typedef struct celeste_prep_wcs_t {
+    int32_t kind;
+    int32_t reserved;
+    double crval[2];                 /* (ra0, dec0), degrees */
+    double crpix[2];                 /* 1-based reference pixel, (h, w) order: FITS axis 1 = h */
+    double cd[4];                    /* degrees per pixel, row-major: CD1_1, CD1_2, CD2_1, CD2_2 */
+} celeste_prep_wcs_t;
 
 typedef struct celeste_prep_source_t {
     double pos[2];
@@ -173,10 +210,20 @@ const char *celeste_prep_strerror(int status);
 int celeste_prep_images_create(int device, int32_t n_images, const celeste_prep_image_t *images, celeste_prep_images_t **handle);
 void celeste_prep_images_destroy(celeste_prep_images_t *handle);
 
+/* The argument checks of celeste_prep_images_set_wcs that need no handle: INVALID_ARG for a null pointer, n_images <= 0, an
+ * unknown kind and, for a TAN entry, a non-finite field, a singular cd or |crval[1]| > 90. */
+int celeste_prep_wcs_check(int32_t n_images, const celeste_prep_wcs_t *wcs);
+/* Gives image n of `handle` the WCS wcs[n] for every later call; n_images must be the handle's count.  Everything is checked
+ * before the device is touched.  A TAN image keeps its wcs_jacobian, wcs_world0 and wcs_pix0 unread. */
+int celeste_prep_images_set_wcs(celeste_prep_images_t *handle, int32_t n_images, const celeste_prep_wcs_t *wcs);
+
 /* The patch table, neighbour lists and (FLAG_STAMPS) stamps of n_sources sources on the images of `handle`. */
 int celeste_prep_patches(celeste_prep_images_t *handle, int64_t n_sources, const celeste_prep_source_t *sources,
                          double radius_override_pix, uint32_t flags, celeste_prep_result_t **result);
 int celeste_prep_result_get(const celeste_prep_result_t *result, celeste_prep_table_t *table);
+/* the entries' Jacobians d pix / d world, [E][4]: J11, J21, J12, J22 (an affine image's entries carry its matrix); NULL for a
+ * result of a handle without a TAN image, whose patches all carry their image's matrix */
+int celeste_prep_result_get_jacobians(const celeste_prep_result_t *result, const double **jac /* [E][4]: J11, J21, J12, J22 */);
 void celeste_prep_result_destroy(celeste_prep_result_t *result);
 
 /* The argument checks of celeste_prep_detected that need no handle: INVALID_ARG for a null pointer, offsets that do not

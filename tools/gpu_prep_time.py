@@ -10,7 +10,10 @@ model.patch_table, PatchTable.neighbors, the per-entry infer.bad_sky loop and in
 field also FieldContext.from_catalog plus the sky flags as infer_box runs them, host path against device path (upload
 included), and infer_box end to end with prep="host" and prep="device".
 The prep library uploads its own copy of the planes (celeste_ctx_create uploads its own as before): `upload_s` is that cost.
-Writes profiles/prep_time_mi355x.json (and prints it).  --small: a 256 x 256 x 5 field only (a rehearsal of the script)."""
+Writes profiles/prep_time_mi355x.json (and prints it).  --small: a 256 x 256 x 5 field only (a rehearsal of the script).
+--wcs tan: only the bench field's geometry (dense table, constant PSF, blank pixels) with the affine WCS and, in the same run,
+with a tangent-plane WCS at dec 60 turned by 30 degrees (model.TanWCS; the same pixel positions): device milliseconds per stage,
+the medians of 21 calls each, taken in turn; the result is added to the JSON file under "wcs_tan" (the rest of the file stays)."""
 import json
 import os
 import sys
@@ -150,10 +153,62 @@ def bench_field(H, W, n, variable):
     return images, catalog
 
 
+def time_wcs(H, W, n, reps=21):
+    """device milliseconds per stage of prep.patch_table on the same pixel positions under an affine and a TAN WCS"""
+    import math
+    affine_cat = catalog_of(H, W, n, 1, 26)
+    t = math.radians(30.0)
+    scale = 0.396 / 3600.0
+    wcs = model.TanWCS((359.9995, 60.0), ((H + 1) / 2.0, (W + 1) / 2.0),
+                       scale * np.array([[math.cos(t), -math.sin(t)], [math.sin(t), math.cos(t)]]))
+    tan_cat = []
+    for ce in affine_cat:
+        tan_cat.append(synthetic.CatalogEntry(wcs.pix_to_world(ce.pos), ce.is_star, ce.star_fluxes, ce.gal_fluxes, ce.gal_frac_dev,
+                                              ce.gal_axis_ratio, ce.gal_angle, ce.gal_radius_px))
+    scenes = {"affine": (synthetic.blank_images(H, W), affine_cat),
+              "tan": ([model.with_tan_wcs(im, wcs) for im in synthetic.blank_images(H, W)], tan_cat)}
+    handles = {k: prep.PrepImages(v[0], 0) for k, v in scenes.items()}
+    ms = {k: [] for k in scenes}
+    tables = {}
+    try:
+        for r in range(reps + 1):
+            for k, (images, catalog) in scenes.items():
+                tables[k] = prep.patch_table(images, catalog, prep_images=handles[k])
+                sync()
+                if r:
+                    ms[k].append(prep.last_ms())
+    finally:
+        for h in handles.values():
+            h.close()
+    out = {"n_images": 5, "n_sources": n, "reps": reps, "entries": int(len(tables["tan"].source))}
+    for k in scenes:
+        out[k] = {"device_ms": {s: float(np.median([m[s] for m in ms[k]])) for s in prep.STAGES if s != "sky"},
+                  "geometry_ms_min_max": [float(min(m["geometry"] for m in ms[k])), float(max(m["geometry"] for m in ms[k]))]}
+    out["tan_over_affine_geometry"] = out["tan"]["device_ms"]["geometry"] / out["affine"]["device_ms"]["geometry"]
+    out["boxes_equal"] = bool(np.array_equal(tables["affine"].box, tables["tan"].box))   # (may differ at a rounding tie)
+    return out
+
+
 def main():
     import torch
     assert torch.cuda.is_available(), "this tool measures on the device"
     out = {"reps": REPS, "device": torch.cuda.get_device_name(0)}
+    if "--wcs" in sys.argv:
+        if sys.argv[sys.argv.index("--wcs") + 1:][:1] != ["tan"]:
+            raise SystemExit("--wcs tan")
+        small = "--small" in sys.argv
+        res = time_wcs(256, 256, 60) if small else time_wcs(2048, 1489, 2000)
+        print(json.dumps({"wcs_tan": res}, indent=1))
+        if not small:
+            path = os.path.join(ROOT, "profiles", "prep_time_mi355x.json")
+            with open(path) as f:
+                doc = json.load(f)
+            doc["wcs_tan"] = res
+            with open(path, "w") as f:
+                json.dump(doc, f, indent=1)
+                f.write("\n")
+            print("wrote", path)
+        return
     if "--small" in sys.argv:
         for variable in (False, True):
             images, catalog = bench_field(256, 256, 60, variable)
