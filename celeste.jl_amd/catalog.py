@@ -87,12 +87,29 @@ def fit_columns(fit) -> Dict[str, Optional[float]]:
             "max_z": num(fit.max_z()), "n_pix": int(fit.n_pix.sum())}
 
 
-def celeste_to_rows(results, diagnostics: bool = False) -> List[Dict[str, Optional[float]]]:
-    """one row per OptimizedSource whose sky is not flagged bad; diagnostics: each row also gets DIAGNOSTIC_COLUMNS"""
+LIGHT_CURVE_COLUMNS = ("n_epochs_r", "var_chi2_r")
+
+
+def light_curve_columns(lc) -> Dict[str, Optional[float]]:
+    """the variability columns of one result (phot.LightCurves of infer_box(..., light_curves=True)) in the r band: the number
+    of exposures with a sound estimate and the chi-square of their scales about the weighted mean (n_epochs_r - 1 degrees of
+    freedom for a source of constant light); None where the result carries no `light_curve` or the quantity is undefined"""
+    if lc is None:
+        return {name: None for name in LIGHT_CURVE_COLUMNS}
+    n, v = int(lc.n_epochs[0, 2]), float(lc.chi2_var[0, 2])
+    return {"n_epochs_r": n, "var_chi2_r": v if math.isfinite(v) else None}
+
+
+def celeste_to_rows(results, diagnostics: bool = False, light_curves: bool = False) -> List[Dict[str, Optional[float]]]:
+    """one row per OptimizedSource whose sky is not flagged bad; diagnostics: each row also gets DIAGNOSTIC_COLUMNS;
+    light_curves: each row also gets LIGHT_CURVE_COLUMNS"""
     rows = [variational_parameters_to_row(r.vs) for r in results if not r.is_sky_bad]
     if diagnostics:
         for row, r in zip(rows, [r for r in results if not r.is_sky_bad]):
             row.update(fit_columns(getattr(r, "fit", None)))
+    if light_curves:
+        for row, r in zip(rows, [r for r in results if not r.is_sky_bad]):
+            row.update(light_curve_columns(getattr(r, "light_curve", None)))
     return rows
 
 

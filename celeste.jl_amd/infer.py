@@ -186,6 +186,7 @@ class OptimizedSource:
     is_sky_bad: bool
     failed: bool = False   # the optimiser reported a non-finite ELBO for this source; vs is its last good row
     fit: Optional[object] = None   # infer_box(..., diagnostics=True): this source's fit.FitStats at the final parameters
+    light_curve: Optional[object] = None   # infer_box(..., light_curves=True): this source's phot.LightCurves (one target)
 
 
 def bad_sky(ce, images) -> bool:
@@ -302,7 +303,7 @@ def group_joint_infer(group, catalog, target_sources: Sequence[int], neighbors: 
 def infer_box(images, box: BoundingBox, catalog=None, method: str = "joint_vi", cfg: Optional[ElboConfig] = None,
               n_iters: int = NUM_JOINT_VI_ITERS, device: int = 0, schedule: str = "cyclades",
               devices: Optional[Sequence[int]] = None, match_radius: float = 1.0 / 3600.0,
-              mcmc_config=None, prep: str = "host", diagnostics: bool = False) -> list:
+              mcmc_config=None, prep: str = "host", diagnostics: bool = False, light_curves: bool = False) -> list:
     """infer_box / _infer_box (ParallelRun.jl:610-672): targets = catalog entries strictly inside the box, neighbours
     may lie outside it, then joint or single variational inference on the device (method in {joint_vi, single_vi}:
     one OptimizedSource per target) or MCMC (method = "mcmc": process_source_mcmc, ParallelRun.jl:504-543, with
@@ -320,19 +321,25 @@ def infer_box(images, box: BoundingBox, catalog=None, method: str = "joint_vi", 
     diagnostics: after variational inference every result also carries `fit`, the goodness of fit of its source
     (fit.FitStats: chi-square, residual flux, purity, flux misfit per band; include/celeste_fit.h) at the final table --
     the targets at their optimised rows, every other source at catalog_init_source -- computed on the first device.  Not
-    available with method="mcmc" (there is no parameter table to evaluate).  The default loads nothing and changes nothing."""
+    available with method="mcmc" (there is no parameter table to evaluate).  The default loads nothing and changes nothing.
+    light_curves: after variational inference every result also carries `light_curve`, the per-exposure forced photometry of
+    its source (phot.LightCurves of one target: per image the scale of its light, its error, a flag; per band the weighted mean
+    and the variability chi-square; include/celeste_phot.h) at the same table.  Not available with method="mcmc".  The default
+    loads nothing and changes nothing."""
     if prep not in ("host", "device"):
         raise ValueError("prep must be 'host' or 'device', not %r" % (prep,))
     if diagnostics and method == "mcmc":
         raise ValueError("diagnostics=True needs a parameter table: method='mcmc' returns samples, not parameters")
+    if light_curves and method == "mcmc":
+        raise ValueError("light_curves=True needs a parameter table: method='mcmc' returns samples, not parameters")
     if method == "mcmc" and devices is not None:
         raise ValueError("method='mcmc' runs on one device: pass device=..., not devices=... (device groups run VI only)")
     if catalog is None:
         if prep == "device":
             return _infer_box_detected_table(images, box, method, cfg, n_iters, device, schedule, devices, match_radius, mcmc_config,
-                                             diagnostics)
+                                             diagnostics, light_curves)
         return _infer_box_detected(images, box, method, cfg, n_iters, device, schedule, devices, match_radius, mcmc_config,
-                                   diagnostics)
+                                   diagnostics, light_curves)
     targets = [i for i, ce in enumerate(catalog) if box.contains(ce.pos)]
     if not targets:
         return []
@@ -340,28 +347,36 @@ def infer_box(images, box: BoundingBox, catalog=None, method: str = "joint_vi", 
         from .prep import PrepImages
         with PrepImages(images, devices[0] if devices is not None else device) as pi:
             return _infer_box_catalog(images, catalog, targets, method, cfg, n_iters, device, schedule, devices, mcmc_config, pi,
-                                      diagnostics)
+                                      diagnostics, light_curves)
     return _infer_box_catalog(images, catalog, targets, method, cfg, n_iters, device, schedule, devices, mcmc_config, None,
-                              diagnostics)
+                              diagnostics, light_curves)
 
 
-def _with_fit(results: list, diagnostics: bool, problem, catalog, targets, device: int) -> list:
+def _with_fit(results: list, diagnostics: bool, problem, catalog, targets, device: int, light_curves: bool = False) -> list:
     """infer_box(..., diagnostics=True): every result gets the fit statistics of its source (fit.FitContext.stats) at the
-    table that holds the targets' optimised rows and catalog_init_source for every other source"""
-    if not diagnostics or not results:
+    table that holds the targets' optimised rows and catalog_init_source for every other source; light_curves=True: its
+    per-exposure photometry (phot.PhotContext.light_curves) at the same table"""
+    if not (diagnostics or light_curves) or not results:
         return results
-    from .fit import FitContext
     vp = init_source_table(catalog)
     vp[list(targets)] = np.stack([r.vs for r in results])
-    with FitContext(problem, device) as fc:
-        st = fc.stats(vp, list(targets))
-    for k, r in enumerate(results):
-        r.fit = st[k]
+    if diagnostics:
+        from .fit import FitContext
+        with FitContext(problem, device) as fc:
+            st = fc.stats(vp, list(targets))
+        for k, r in enumerate(results):
+            r.fit = st[k]
+    if light_curves:
+        from .phot import PhotContext
+        with PhotContext(problem, device) as pc:
+            lc = pc.light_curves(vp, list(targets))
+        for k, r in enumerate(results):
+            r.light_curve = lc[k]
     return results
 
 
 def _infer_box_catalog(images, catalog, targets, method, cfg, n_iters, device, schedule, devices, mcmc_config, pi,
-                       diagnostics: bool = False) -> list:
+                       diagnostics: bool = False, light_curves: bool = False) -> list:
     """infer_box with a catalog.  pi: a prep.PrepImages over `images` (the table, neighbour lists, stamps and sky flags come
     from the device) or None (from the host)."""
     def sky_flags(dev):
@@ -396,7 +411,7 @@ def _infer_box_catalog(images, catalog, targets, method, cfg, n_iters, device, s
             group.close()
         flags = sky_flags(devices[0])
         return _with_fit([OptimizedSource(float(catalog[t].pos[0]), float(catalog[t].pos[1]), vs[k].copy(), flags[k], t in failed)
-                          for k, t in enumerate(targets)], diagnostics, group.problem, catalog, targets, devices[0])
+                          for k, t in enumerate(targets)], diagnostics, group.problem, catalog, targets, devices[0], light_curves)
     # patches and neighbour lists as arrays (model.patch_table: the geometry of get_sky_patches / find_neighbors
     # without a Python object per patch); several fields: sources see a few images each -> sparse patch list
     ctx = FieldContext.from_catalog(images, catalog, device=device, sparse=len(images) > 5, prep_images=pi)
@@ -414,11 +429,11 @@ def _infer_box_catalog(images, catalog, targets, method, cfg, n_iters, device, s
         ctx.close()
     flags = sky_flags(device)
     return _with_fit([OptimizedSource(float(catalog[t].pos[0]), float(catalog[t].pos[1]), vs[k].copy(), flags[k], t in failed)
-                      for k, t in enumerate(targets)], diagnostics, ctx.problem, catalog, targets, device)
+                      for k, t in enumerate(targets)], diagnostics, ctx.problem, catalog, targets, device, light_curves)
 
 
 def _infer_box_detected(images, box: BoundingBox, method, cfg, n_iters, device, schedule, devices,
-                        match_radius, mcmc_config=None, diagnostics: bool = False) -> list:
+                        match_radius, mcmc_config=None, diagnostics: bool = False, light_curves: bool = False) -> list:
     """_infer_box with the catalog and patches of detect_sources (ParallelRun.jl:661-665): targets strictly inside the
     box, neighbours from the detection patches, the context (or device group) over those patches."""
     from .detect import detect_sources
@@ -470,11 +485,11 @@ def _infer_box_detected(images, box: BoundingBox, method, cfg, n_iters, device, 
         flag_device = device
     flags = bad_sky_flags([catalog[t] for t in targets], images, flag_device)
     return _with_fit([OptimizedSource(float(catalog[t].pos[0]), float(catalog[t].pos[1]), vs[k].copy(), flags[k], t in failed)
-                      for k, t in enumerate(targets)], diagnostics, problem, catalog, targets, flag_device)
+                      for k, t in enumerate(targets)], diagnostics, problem, catalog, targets, flag_device, light_curves)
 
 
 def _infer_box_detected_table(images, box: BoundingBox, method, cfg, n_iters, device, schedule, devices,
-                              match_radius, mcmc_config=None, diagnostics: bool = False) -> list:
+                              match_radius, mcmc_config=None, diagnostics: bool = False, light_curves: bool = False) -> list:
     """_infer_box_detected with the join, the catalog, the patch table, the neighbour lists and the sky flags from the device
     (detect.detect_table, prep.bad_sky_flags over one prep.PrepImages); the problem is cabi.problem_from_table's."""
     from . import cabi, prep
@@ -521,4 +536,4 @@ def _infer_box_detected_table(images, box: BoundingBox, method, cfg, n_iters, de
                 ctx.close()
         flags = prep.bad_sky_flags([catalog[t] for t in targets], images, prep_images=pi)
     return _with_fit([OptimizedSource(float(catalog[t].pos[0]), float(catalog[t].pos[1]), vs[k].copy(), flags[k], t in failed)
-                      for k, t in enumerate(targets)], diagnostics, problem, catalog, targets, first)
+                      for k, t in enumerate(targets)], diagnostics, problem, catalog, targets, first, light_curves)
