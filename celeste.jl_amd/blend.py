@@ -16,7 +16,7 @@ from typing import Optional, Sequence
 
 import numpy as np
 
-from . import cabi
+from . import _binding, cabi
 from .cabi import FLAG_GRAD, FLAG_HESS, FLAG_KL, P
 
 LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc", "blend", "libceleste_blend.so")
@@ -26,25 +26,12 @@ NF = 41                    # free parameters per member
 EXPORTED_SYMBOLS = ["celeste_blend_version", "celeste_blend_strerror", "celeste_blend_ctx_create", "celeste_blend_ctx_destroy",
                     "celeste_blend_eval", "celeste_blend_maximize", "celeste_blend_tr_solve_batch", "celeste_blend_last_ms"]
 
-_lib = None
 _dp, _ip, _lp = cabi.c_double_p, cabi.c_int32_p, cabi.c_int64_p
+_ptr = _binding.ptr
+_check = _binding.checker("blend")
 
 
-def load_library(path: Optional[str] = None) -> C.CDLL:
-    """libceleste_blend.so; CELESTE_MI355X_BLEND_LIB overrides its path.  torch's HIP runtime is loaded first (cabi)."""
-    global _lib
-    if _lib is not None and path is None:
-        return _lib
-    path = path or os.environ.get("CELESTE_MI355X_BLEND_LIB") or LIB_PATH
-    if not os.path.exists(path):
-        raise ImportError("HIP extension %s is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
-                          "(hipcc --offload-arch=gfx950). There is no CPU fallback." % path)
-    cabi.load_library()
-    lib = C.CDLL(path)
-    lib.celeste_blend_version.restype = C.c_int
-    if lib.celeste_blend_version() // 100 != ABI_VERSION // 100:
-        raise ImportError("%s has ABI version %d, this binding was written against %d" % (path, lib.celeste_blend_version(),
-                                                                                           ABI_VERSION))
+def _declare(lib):
     vp = C.c_void_p
     lib.celeste_blend_strerror.restype = C.c_char_p
     lib.celeste_blend_strerror.argtypes = [C.c_int]
@@ -56,17 +43,11 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
                                            _ip]
     lib.celeste_blend_last_ms.argtypes = [vp, C.POINTER(C.c_float)]
     lib.celeste_blend_tr_solve_batch.argtypes = [C.c_int, C.c_int32, _ip, _dp, _dp, _dp, C.c_int32, C.c_int32, _dp, _dp, _ip]
-    _lib = lib
-    return lib
 
 
-def _check(lib, st: int):
-    if st != 0:
-        raise RuntimeError("libceleste_blend: %s (status %d)" % (lib.celeste_blend_strerror(st).decode(), st))
-
-
-def _ptr(a, t):
-    return None if a is None else a.ctypes.data_as(t)
+def load_library(path: Optional[str] = None) -> C.CDLL:
+    """libceleste_blend.so; CELESTE_MI355X_BLEND_LIB overrides its path (_binding.open_library)"""
+    return _binding.open_library("blend", LIB_PATH, "CELESTE_MI355X_BLEND_LIB", ABI_VERSION, "celeste_blend_version", _declare, path)
 
 
 def blend_arrays(blends: Sequence[Sequence[int]]):
@@ -100,32 +81,9 @@ def tr_solve_batch(Hs, gs, deltas, secular_iters: int = 0, device: int = 0):
     return out, m, interior
 
 
-class BlendContext:
+class BlendContext(_binding.Context):
     """The blend library's copy of a problem (celeste_blend_ctx_t), built from a marshalled celeste_problem_t."""
-
-    def __init__(self, problem: "cabi.Problem", device: int = 0):
-        self.lib = load_library()
-        self.problem = problem
-        self.S = problem.n_sources
-        self._keep: list = []
-        pc = cabi.ProblemT.from_buffer_copy(problem.c)
-        if not pc.images:
-            pc.images = cabi.marshal_image_structs(problem.images, self._keep)
-        self._pc = pc
-        h = C.c_void_p()
-        _check(self.lib, self.lib.celeste_blend_ctx_create(C.byref(pc), int(device), C.byref(h)))
-        self.handle = h
-
-    def close(self):
-        if getattr(self, "handle", None):
-            self.lib.celeste_blend_ctx_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+    _name, _load = "blend", staticmethod(load_library)
 
     def eval_blends(self, vp, blends: Sequence[Sequence[int]], flags: int = FLAG_GRAD | FLAG_HESS | FLAG_KL,
                     raise_on_error: bool = True):

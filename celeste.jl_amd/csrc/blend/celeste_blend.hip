@@ -1,7 +1,7 @@
 // celeste_blend.hip -- libceleste_blend.so: maximize! with several active sources (include/celeste_blend.h).
 //
-// The engine's context and evaluation code (celeste_abi.hip) is compiled into this library, unchanged; this file adds the
-// blend driver and two kernels of its own.  Per Newton iteration, for every live blend of the call at once:
+// The engine's context and evaluation code (celeste_abi.hip) is compiled into this library, unchanged; the context with its
+// device buffers is engine_client.h's; this file adds the blend driver and two kernels of its own.  Per Newton iteration, for every live blend of the call at once:
 //   launch_eval (MULTI)        the members of all live blends as one target list; every member's pixel sums with the
 //                              multi-active rule "an earlier active source visits this pixel" (elbo_kernels.h).  The
 //                              refusal rule (no member is a neighbour of a member of another blend) means a member's
@@ -16,6 +16,7 @@
 // The (44 Sa)^2 blocks and the (41 Sa)^2 free Hessians stay in HBM; the host waits once per iteration for the blends'
 // phases.  No floating-point atomics: every sum runs in a fixed order.
 #include "../celeste_abi.hip"
+#include "../engine_client.h"
 #include "../../../include/celeste_blend.h"
 
 #define BL_SA_MAX CELESTE_BLEND_SA_MAX
@@ -499,66 +500,24 @@ __global__ __launch_bounds__(BL_NT) void blend_assemble_kernel(
 }
 
 // ---- host side ----------------------------------------------------------------------------------------------------------
-struct BlBuf { void *p = nullptr; size_t cap = 0; };
-
-struct celeste_blend_ctx {
-    celeste_ctx_t *c = nullptr;
-    BlBuf buf[32];
+// last_ms of the last celeste_blend_maximize: evaluation launches, step launches (device time, summed over iterations), iterations
+struct celeste_blend_ctx : ClientCtx<32, 3, 3> {
     // host staging of one evaluation launch set: kept here, not on the stack, so that it outlives the asynchronous copies
     // (the next launch set is built only after the stream has been waited for)
     std::vector<int32_t> tg, psa, psb;
     std::vector<BlendDesc> desc;
     std::vector<BlendPair> pairs;
-    // timing of the last celeste_blend_maximize: evaluation launches, step launches (device time, summed over iterations)
-    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
-    float last_ms[3] = {0, 0, 0};
 };
-
-template <class T>
-static hipError_t bl_get(celeste_blend_ctx_t *b, int k, size_t bytes, T **out) {
-    BlBuf &s = b->buf[k];
-    if (bytes > s.cap) {
-        hipError_t e = hipStreamSynchronize(b->c->stream);
-        if (e != hipSuccess) return e;
-        if (s.p) { (void)hipFree(s.p); s.p = nullptr; s.cap = 0; }
-        const size_t cap = std::max<size_t>(bytes, 256);
-        e = hipMalloc(&s.p, cap);
-        if (e != hipSuccess) return e;
-        s.cap = cap;
-    }
-    *out = (T *)s.p;
-    return hipSuccess;
-}
 
 extern "C" int celeste_blend_version(void) { return CELESTE_BLEND_ABI_VERSION; }
 
 extern "C" const char *celeste_blend_strerror(int status) { return celeste_strerror(status); }
 
 extern "C" int celeste_blend_ctx_create(const celeste_problem_t *problem, int device, celeste_blend_ctx_t **out) try {
-    if (!out) return CELESTE_ERR_INVALID_ARG;
-    *out = nullptr;
-    celeste_ctx_t *c = nullptr;
-    const int rc = celeste_ctx_create(problem, device, &c);
-    if (rc != CELESTE_OK) return rc;
-    celeste_blend_ctx_t *b = new celeste_blend_ctx_t();
-    b->c = c;
-    for (auto &e : b->ev)
-        if (hipEventCreate(&e) != hipSuccess) { celeste_blend_ctx_destroy(b); return CELESTE_ERR_HIP; }
-    *out = b;
-    return CELESTE_OK;
+    return client_create(problem, device, out);
 } ABI_CATCH
 
-extern "C" void celeste_blend_ctx_destroy(celeste_blend_ctx_t *b) {
-    if (!b) return;
-    if (b->c) {
-        (void)hipSetDevice(b->c->device);
-        (void)hipStreamSynchronize(b->c->stream);
-        for (auto &s : b->buf) if (s.p) (void)hipFree(s.p);
-        for (auto &e : b->ev) if (e) (void)hipEventDestroy(e);
-        celeste_ctx_destroy(b->c);
-    }
-    delete b;
-}
+extern "C" void celeste_blend_ctx_destroy(celeste_blend_ctx_t *b) { client_destroy(b); }
 
 // The blends of a call, checked: members in call order, the blend and the slot of each, the overlapping pairs of each blend.
 struct BlendPlan {
@@ -651,13 +610,13 @@ static int bl_eval_launch(celeste_blend_ctx_t *bc, const double *d_table, const 
     o.nt = (int)nt; o.np = (int)np;
     int32_t *d_t = nullptr, *d_pa = nullptr, *d_pb = nullptr;
     double *d_rec = nullptr;
-    if (bl_get(bc, 0, nt * sizeof(int32_t), &d_t) != hipSuccess || bl_get(bc, 1, nt * sizeof(double), &o.v) != hipSuccess ||
-        bl_get(bc, 2, nt * CEL_P * sizeof(double), &o.d) != hipSuccess ||
-        bl_get(bc, 3, (want_hess ? nt : 1) * CEL_P * CEL_P * sizeof(double), &o.h) != hipSuccess ||
-        bl_get(bc, 4, nt * 2 * sizeof(int64_t), &o.cnt) != hipSuccess || bl_get(bc, 5, nt * sizeof(int32_t), &o.st) != hipSuccess ||
-        bl_get(bc, 6, desc.size() * sizeof(BlendDesc), &o.desc) != hipSuccess ||
-        bl_get(bc, 7, std::max<size_t>(np, 1) * sizeof(BlendPair), &o.pairs) != hipSuccess ||
-        bl_get(bc, 8, std::max<size_t>(np, 1) * LIFT_NP * LIFT_NP * sizeof(double), &o.x) != hipSuccess)
+    if (client_get(bc, 0, nt * sizeof(int32_t), &d_t) != hipSuccess || client_get(bc, 1, nt * sizeof(double), &o.v) != hipSuccess ||
+        client_get(bc, 2, nt * CEL_P * sizeof(double), &o.d) != hipSuccess ||
+        client_get(bc, 3, (want_hess ? nt : 1) * CEL_P * CEL_P * sizeof(double), &o.h) != hipSuccess ||
+        client_get(bc, 4, nt * 2 * sizeof(int64_t), &o.cnt) != hipSuccess || client_get(bc, 5, nt * sizeof(int32_t), &o.st) != hipSuccess ||
+        client_get(bc, 6, desc.size() * sizeof(BlendDesc), &o.desc) != hipSuccess ||
+        client_get(bc, 7, std::max<size_t>(np, 1) * sizeof(BlendPair), &o.pairs) != hipSuccess ||
+        client_get(bc, 8, std::max<size_t>(np, 1) * LIFT_NP * LIFT_NP * sizeof(double), &o.x) != hipSuccess)
         return CELESTE_ERR_HIP;
     HIP_TRY(hipMemcpyAsync(d_t, tg.data(), nt * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipMemcpyAsync(o.desc, desc.data(), desc.size() * sizeof(BlendDesc), hipMemcpyHostToDevice, c->stream));
@@ -665,8 +624,8 @@ static int bl_eval_launch(celeste_blend_ctx_t *bc, const double *d_table, const 
                                true, d_rank);
     if (rc != CELESTE_OK) return rc;
     if (np > 0) {
-        if (bl_get(bc, 9, np * sizeof(int32_t), &d_pa) != hipSuccess || bl_get(bc, 10, np * sizeof(int32_t), &d_pb) != hipSuccess ||
-            bl_get(bc, 11, np * c->N * ZV * ZV * sizeof(double), &d_rec) != hipSuccess)
+        if (client_get(bc, 9, np * sizeof(int32_t), &d_pa) != hipSuccess || client_get(bc, 10, np * sizeof(int32_t), &d_pb) != hipSuccess ||
+            client_get(bc, 11, np * c->N * ZV * ZV * sizeof(double), &d_rec) != hipSuccess)
             return CELESTE_ERR_HIP;
         HIP_TRY(hipMemcpyAsync(o.pairs, pairs.data(), np * sizeof(BlendPair), hipMemcpyHostToDevice, c->stream));
         HIP_TRY(hipMemcpyAsync(d_pa, psa.data(), np * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
@@ -683,7 +642,7 @@ static int bl_eval_launch(celeste_blend_ctx_t *bc, const double *d_table, const 
 
 static int bl_upload_rank(celeste_blend_ctx_t *bc, const BlendPlan &P, int32_t **d_rank) {
     celeste_ctx_t *c = bc->c;
-    if (bl_get(bc, 12, (size_t)c->S * sizeof(int32_t), d_rank) != hipSuccess) return CELESTE_ERR_HIP;
+    if (client_get(bc, 12, (size_t)c->S * sizeof(int32_t), d_rank) != hipSuccess) return CELESTE_ERR_HIP;
     HIP_TRY(hipMemcpyAsync(*d_rank, P.rank.data(), (size_t)c->S * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
     return CELESTE_OK;
 }
@@ -706,12 +665,12 @@ extern "C" int celeste_blend_eval(celeste_blend_ctx_t *bc, const double *vp, int
     int32_t *d_rank = nullptr, *d_so = nullptr;
     std::vector<int64_t> hoff(n_blends + 1, 0);
     for (int b = 0; b < n_blends; ++b) hoff[b + 1] = hoff[b] + (int64_t)CEL_P * P.sa[b] * CEL_P * P.sa[b];
-    if (bl_get(bc, 13, (size_t)c->S * CEL_P * sizeof(double), &d_table) != hipSuccess ||
-        bl_get(bc, 14, n_blends * sizeof(double), &d_vo) != hipSuccess ||
-        bl_get(bc, 15, (want_hess ? hoff[n_blends] : 1) * sizeof(double), &d_ho) != hipSuccess ||
-        bl_get(bc, 16, (n_blends + 1) * sizeof(int64_t), &d_hoff) != hipSuccess ||
-        bl_get(bc, 17, 2 * n_blends * sizeof(int64_t), &d_co) != hipSuccess ||
-        bl_get(bc, 18, n_blends * sizeof(int32_t), &d_so) != hipSuccess)
+    if (client_get(bc, 13, (size_t)c->S * CEL_P * sizeof(double), &d_table) != hipSuccess ||
+        client_get(bc, 14, n_blends * sizeof(double), &d_vo) != hipSuccess ||
+        client_get(bc, 15, (want_hess ? hoff[n_blends] : 1) * sizeof(double), &d_ho) != hipSuccess ||
+        client_get(bc, 16, (n_blends + 1) * sizeof(int64_t), &d_hoff) != hipSuccess ||
+        client_get(bc, 17, 2 * n_blends * sizeof(int64_t), &d_co) != hipSuccess ||
+        client_get(bc, 18, n_blends * sizeof(int32_t), &d_so) != hipSuccess)
         return CELESTE_ERR_HIP;
     HIP_TRY(hipMemcpyAsync(d_table, vp, (size_t)c->S * CEL_P * sizeof(double), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipMemcpyAsync(d_hoff, hoff.data(), (n_blends + 1) * sizeof(int64_t), hipMemcpyHostToDevice, c->stream));
@@ -732,8 +691,7 @@ extern "C" int celeste_blend_eval(celeste_blend_ctx_t *bc, const double *vp, int
     if (want_grad) HIP_TRY(hipMemcpyAsync(d, o.d, (size_t)P.M * CEL_P * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     if (want_hess) HIP_TRY(hipMemcpyAsync(h, d_ho, hoff[n_blends] * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
-    for (int b = 0; b < n_blends; ++b) if (status[b] != CELESTE_OK) return status[b];
-    return CELESTE_OK;
+    return client_first_status(status, n_blends);
 } ABI_CATCH
 
 extern "C" int celeste_blend_maximize(celeste_blend_ctx_t *bc, double *vp, const double *vp_neighbors,
@@ -770,19 +728,19 @@ extern "C" int celeste_blend_maximize(celeste_blend_ctx_t *bc, double *vp, const
            *d_H = nullptr, *d_A = nullptr, *d_V = nullptr, *d_J = nullptr, *d_W = nullptr;
     int32_t *d_members = nullptr, *d_mb = nullptr, *d_ms = nullptr, *d_rank = nullptr;
     BlendState *d_state = nullptr;
-    if (bl_get(bc, 13, (size_t)c->S * CEL_P * sizeof(double), &d_table) != hipSuccess ||
-        bl_get(bc, 19, (size_t)M * CEL_P * sizeof(double), &d_orig) != hipSuccess ||
-        bl_get(bc, 20, (size_t)M * 2 * sizeof(double), &d_pos) != hipSuccess ||
-        bl_get(bc, 21, (size_t)M * 2 * sizeof(double), &d_pos0) != hipSuccess ||
-        bl_get(bc, 22, (size_t)B * 2 * BL_NMAX * sizeof(double), &d_X) != hipSuccess ||
-        bl_get(bc, 23, (size_t)B * 2 * BL_NMAX * sizeof(double), &d_G) != hipSuccess ||
-        bl_get(bc, 24, (size_t)B * 2 * NN * sizeof(double), &d_H) != hipSuccess ||
-        bl_get(bc, 25, (size_t)B * NN * sizeof(double), &d_A) != hipSuccess ||
-        bl_get(bc, 26, (size_t)B * NN * sizeof(double), &d_V) != hipSuccess ||
-        bl_get(bc, 27, (size_t)B * BL_SA_MAX * BL_JN * sizeof(double), &d_J) != hipSuccess ||
-        bl_get(bc, 28, (size_t)B * BL_JN * sizeof(double), &d_W) != hipSuccess ||
-        bl_get(bc, 29, (size_t)M * 3 * sizeof(int32_t), &d_members) != hipSuccess ||
-        bl_get(bc, 30, (size_t)B * sizeof(BlendState), &d_state) != hipSuccess)
+    if (client_get(bc, 13, (size_t)c->S * CEL_P * sizeof(double), &d_table) != hipSuccess ||
+        client_get(bc, 19, (size_t)M * CEL_P * sizeof(double), &d_orig) != hipSuccess ||
+        client_get(bc, 20, (size_t)M * 2 * sizeof(double), &d_pos) != hipSuccess ||
+        client_get(bc, 21, (size_t)M * 2 * sizeof(double), &d_pos0) != hipSuccess ||
+        client_get(bc, 22, (size_t)B * 2 * BL_NMAX * sizeof(double), &d_X) != hipSuccess ||
+        client_get(bc, 23, (size_t)B * 2 * BL_NMAX * sizeof(double), &d_G) != hipSuccess ||
+        client_get(bc, 24, (size_t)B * 2 * NN * sizeof(double), &d_H) != hipSuccess ||
+        client_get(bc, 25, (size_t)B * NN * sizeof(double), &d_A) != hipSuccess ||
+        client_get(bc, 26, (size_t)B * NN * sizeof(double), &d_V) != hipSuccess ||
+        client_get(bc, 27, (size_t)B * BL_SA_MAX * BL_JN * sizeof(double), &d_J) != hipSuccess ||
+        client_get(bc, 28, (size_t)B * BL_JN * sizeof(double), &d_W) != hipSuccess ||
+        client_get(bc, 29, (size_t)M * 3 * sizeof(int32_t), &d_members) != hipSuccess ||
+        client_get(bc, 30, (size_t)B * sizeof(BlendState), &d_state) != hipSuccess)
         return CELESTE_ERR_HIP;
     d_mb = d_members + M;
     d_ms = d_members + 2 * M;
@@ -842,11 +800,7 @@ extern "C" int celeste_blend_maximize(celeste_blend_ctx_t *bc, double *vp, const
     return first;
 } ABI_CATCH
 
-extern "C" int celeste_blend_last_ms(celeste_blend_ctx_t *bc, float ms[3]) {
-    if (!bc || !ms) return CELESTE_ERR_INVALID_ARG;
-    for (int k = 0; k < 3; ++k) ms[k] = bc->last_ms[k];
-    return CELESTE_OK;
-}
+extern "C" int celeste_blend_last_ms(celeste_blend_ctx_t *bc, float ms[3]) { return client_last_ms(bc, ms); }
 
 extern "C" int celeste_blend_tr_solve_batch(int device, int32_t n, const int32_t *dims, const double *H, const double *g,
                                             const double *delta, int32_t solver, int32_t secular_iters, double *p, double *m,

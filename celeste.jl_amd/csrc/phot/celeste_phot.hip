@@ -2,13 +2,13 @@
 //
 // The engine's context and evaluation code (celeste_abi.hip) is compiled into this library, unchanged, as for the fit and
 // blend libraries: the patch table, the per-visit tables of prep_kernel, the spline coefficients, the bitmaps, the neighbour
-// lists, star_value and galaxy_value are the engine's.  This file adds a work list and three kernels.  One call:
+// lists, star_value and galaxy_value are the engine's.  The context, the work list and the pixel walk (the target's own light
+// m and the neighbours' light B of every pixel) are engine_client.h's; this file adds three kernels.  One call:
 //   prep_kernel          (the engine's) SrcImg and Comp of every visit of the context at the call's table
-//   phot_pixel_kernel    one wavefront per work item = (visit of a target, chunk of CELESTE_CHUNK_PX pixels of its patch), as
-//                        fit_pixel_kernel: a lane owns a pixel; it forms the target's own light m and the neighbours' light B
-//                        -- the expensive part, once per pixel -- and writes a = iota m, b = iota (eps + B) and x to the
-//                        entry's scratch in device memory (CSR by entry, one plane each); a pixel that is not visited is
-//                        written as a = b = x = 0 (b > 0 marks a visited pixel of a sound entry)
+//   phot_pixel_kernel    one wavefront per work item; from m and B -- the expensive part, once per pixel -- a lane writes
+//                        a = iota m, b = iota (eps + B) and x to the entry's scratch in device memory (CSR by entry, one plane
+//                        each); a pixel that is not visited is written as a = b = x = 0 (b > 0 marks a visited pixel of a
+//                        sound entry)
 //   phot_solve_kernel    one workgroup of four wavefronts per entry runs every Newton iteration.  <true>: a, b, x are staged
 //                        once into LDS (24 B per pixel, up to CELESTE_PHOT_LDS_PIXELS pixels); <false>: they are read from
 //                        the scratch on every iteration.  Both run the same pass: wavefront w sums tiles w, w + 4, ... (a tile
@@ -19,6 +19,7 @@
 //   phot_summary_kernel  one wavefront per target: lane b adds the OK entries of band b in ascending image order; status
 // No floating-point atomics; every rounded operation of a pass is spelled out (no contraction), so both paths agree bit for bit.
 #include "../celeste_abi.hip"
+#include "../engine_client.h"
 #include "../../../include/celeste_phot.h"
 
 #define PHOT_NB CELESTE_PHOT_BANDS
@@ -27,13 +28,6 @@
 #define PHOT_WAVES (PHOT_THREADS / 64)
 #define PHOT_PT 128                     // tiles of a round: 2 buffers x 128 tiles x 3 sums x 8 B = 6 KiB of LDS
 #define PHOT_CLASSES 4                  // size classes of the LDS path: one launch each
-
-struct PhotItem {
-    int32_t sn, n;                     // visit (table entry of the target's patch), image
-    int32_t p0;                        // first pixel of the chunk
-    int32_t tile0;                     // the chunk's first tile
-    int64_t px_off;                    // where the entry's pixels start in the scratch planes
-};
 
 struct PhotEntry {
     int64_t px_off;                    // first pixel in the scratch planes
@@ -44,74 +38,23 @@ struct PhotEntry {
 
 struct PhotTileInfo { int32_t n_pix, bad; };   // visited pixels; a or b unsound at one of them
 
-__device__ __forceinline__ double phot_light(const SrcImg &si, const Comp *tc, int NC, const double *__restrict__ coef,
-                                             const double *etab, double hh, double ww) {
-    const double f0 = star_value(coef, hh + (26.0 - si.m1), ww + (26.0 - si.m2));
-    const double f1 = galaxy_value(tc, NC, hh - si.m1, ww - si.m2, etab);
-    return si.c0 * f0 + si.c1 * f1;
-}
-
-__device__ __forceinline__ void phot_stage_comps(Comp *dst, const Comp *__restrict__ src, int NC) {
-    const double *s = reinterpret_cast<const double *>(src);
-    double *d = reinterpret_cast<double *>(dst);
-    for (int i = threadIdx.x; i < NC * 8; i += 64) d[i] = s[i];
-}
-
 // ---- pixel pass ------------------------------------------------------------------------------------------------------------
+// (a work item's px_off: where the entry's pixels start in the scratch planes)
 __global__ void __launch_bounds__(64)
-phot_pixel_kernel(const PhotItem *__restrict__ items, const DevImage *__restrict__ images, const DevPatch *__restrict__ patches,
+phot_pixel_kernel(const VisitItem *__restrict__ items, const DevImage *__restrict__ images, const DevPatch *__restrict__ patches,
                   const double *__restrict__ coefs, const uint8_t *__restrict__ bitmaps, const SrcImg *__restrict__ srcimg,
                   const Comp *__restrict__ comps, const int64_t *__restrict__ nbr_off, const int32_t *__restrict__ nbr_idx,
                   const int32_t *__restrict__ vis_off, const int32_t *__restrict__ vis_img, const int32_t *__restrict__ vis_src,
                   int dense, int N, int NC, int chunk_px, double *__restrict__ sa, double *__restrict__ sb,
                   double *__restrict__ sx, PhotTileInfo *__restrict__ info) {
-    __shared__ double etab[64];
-    __shared__ Comp tc[14 * CEL_MAXK];     // the target's components
-    __shared__ Comp tq[14 * CEL_MAXK];     // the current neighbour's
-    const PhotItem it = items[blockIdx.x];
+    const VisitItem it = items[blockIdx.x];
     const int lane = threadIdx.x;
-    const int sn = it.sn, n = it.n;
-    const int s = vis_src[sn];
-    const DevPatch &P = patches[sn];
-    const DevImage &img = images[n];
-    const int H2 = P.H2, W2 = P.W2, npx = H2 * W2;
-    const int p1 = min(npx, it.p0 + chunk_px);
-    const float rH2 = 1.0f / (float)H2;
-    exp_table_init(etab);
-    const SrcImg si = srcimg[sn];
-    phot_stage_comps(tc, comps + (size_t)sn * NC, NC);
-    __syncthreads();
-    const double *__restrict__ coef = coefs + (size_t)P.stamp * (CEL_COEF * CEL_COEF);
-    const int64_t nb0 = nbr_off[s], nb1 = nbr_off[s + 1];
-    int tile = it.tile0;
-    for (int base = it.p0; base < p1; base += 64, ++tile) {
-        const int idx = base + lane;
-        const bool inp = idx < p1;
-        int w2, h2;                                           // 0-based in the patch
-        divmod_small(min(idx, npx - 1), H2, rH2, w2, h2);
-        const int h0 = P.off_h + h2, w0 = P.off_w + w2;       // 0-based in the image
-        const size_t gi = (size_t)h0 + (size_t)img.H * w0;
-        const float xf = img.pixels[gi], skyf = img.sky[gi];
-        const double iota = (double)img.iota[h0];
-        bool valid = inp && !isnan(xf);
-        if (valid && P.bitmap_off >= 0) valid = bitmaps[P.bitmap_off + h2 + (int64_t)H2 * w2] != 0;
-        const double hh = (double)(h0 + 1), ww = (double)(w0 + 1);
-        double m = 0.0;
-        if (valid && w2 < W2 - 1) m = phot_light(si, tc, NC, coef, etab, hh, ww);   // not in the patch's last column
-        double B = 0.0;
-        for (int64_t q = nb0; q < nb1; ++q) {
-            const int v2 = table_entry(vis_off, vis_img, dense, N, nbr_idx[q], n);
-            if (v2 < 0) continue;
-            const DevPatch &Q = patches[v2];
-            const int qa = h0 - Q.off_h, qb = w0 - Q.off_w;   // 0-based in the neighbour's patch
-            bool in = valid & (qa >= 0) & (qa < Q.H2) & (qb >= 0) & (qb < Q.W2 - 1);
-            if (in && Q.bitmap_off >= 0) in = bitmaps[Q.bitmap_off + qa + (int64_t)Q.H2 * qb] != 0;
-            if (!__any(in)) continue;                         // (the workgroup is one wavefront: uniform)
-            __syncthreads();
-            phot_stage_comps(tq, comps + (size_t)v2 * NC, NC);
-            __syncthreads();
-            if (in) B += phot_light(srcimg[v2], tq, NC, coefs + (size_t)Q.stamp * (CEL_COEF * CEL_COEF), etab, hh, ww);
-        }
+    visit_pixel_walk(it, images, patches, coefs, bitmaps, srcimg, comps, nbr_off, nbr_idx, vis_off, vis_img, vis_src, dense, N, NC,
+                     chunk_px, [&](const DevImage &, const VisitPixel &px) {
+        const int tile = px.tile, idx = px.idx;
+        const bool inp = px.inp, valid = px.valid;
+        const float xf = px.xf, skyf = px.skyf;
+        const double iota = px.iota, m = px.m, B = px.B;
         const double a = __dmul_rn(iota, m), b = __dmul_rn(iota, (double)skyf + B);
         const bool bad = valid && !(isfinite(a) && isfinite(b) && a >= 0.0 && b > 0.0);
         if (inp) {                                            // idx < npx: inside the entry's planes
@@ -127,16 +70,10 @@ phot_pixel_kernel(const PhotItem *__restrict__ items, const DevImage *__restrict
             ti.n_pix = n_valid; ti.bad = any_bad;
             info[tile] = ti;
         }
-    }
+    });
 }
 
 // ---- solve pass ------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ double phot_wave_max(double x) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) x = fmax(x, __shfl_xor(x, o, 64));
-    return x;
-}
-
 // One pass over the entry's pixels at alpha.  MODE 0: s0 = g, s1 = D, s2 = I.  MODE 1: s0 = I, s1 = chi2.
 // part: the two round buffers; round: the running round count of the workgroup (selects the buffer).
 template <int MODE>
@@ -198,7 +135,7 @@ phot_solve_kernel(const int32_t *__restrict__ list, const PhotEntry *__restrict_
     const int npx = E.npx, n_tiles = (npx + 63) >> 6;
     if (tid < 2) cnt[tid] = 0;
     const double *vs = vp + (size_t)targets[E.ti] * CEL_P;
-    const int nonfinite = __syncthreads_or(tid < CEL_P && !isfinite(vs[tid < CEL_P ? tid : 0]));
+    const int nonfinite = __syncthreads_or(row_nonfinite(vs, tid));
     {
         int np = 0, bd = 0;
         for (int t = tid; t < n_tiles; t += PHOT_THREADS) { const PhotTileInfo ti = info[E.tile0 + t]; np += ti.n_pix; bd |= ti.bad; }
@@ -234,7 +171,7 @@ phot_solve_kernel(const int32_t *__restrict__ list, const PhotEntry *__restrict_
                 if (px[p] > 0.0) elec = 1;
             }
         }
-        amin = phot_wave_max(amin);
+        amin = wave_max(amin);
         if (lane == 0) red[wave] = amin;
         light = __syncthreads_or(light);
         elec = __syncthreads_or(elec);
@@ -291,7 +228,7 @@ phot_summary_kernel(const int64_t *__restrict__ eoff, const int32_t *__restrict_
     for (int64_t e = e0 + lane; e < e1; e += 64) bad |= flag[e] == CELESTE_PHOT_BAD_MODEL;
     bad = __any(bad);
     const double *vs = vp + (size_t)targets[ti] * CEL_P;
-    const int nonfinite = __any(lane < CEL_P && !isfinite(vs[lane < CEL_P ? lane : 0]));
+    const int nonfinite = __any(row_nonfinite(vs, lane));
     if (lane < PHOT_NB) {
         int n = 0;
         double W = 0.0, SA = 0.0;
@@ -323,73 +260,35 @@ phot_summary_kernel(const int64_t *__restrict__ eoff, const int32_t *__restrict_
 }
 
 // ---- host side ----------------------------------------------------------------------------------------------------------
-struct PhotBuf { void *p = nullptr; size_t cap = 0; };
-
 enum { PB_VP, PB_ITEMS, PB_ENTRIES, PB_INFO, PB_SA, PB_SB, PB_SX, PB_LIST, PB_TARGETS, PB_EOFF, PB_IMAGE, PB_BAND, PB_ALPHA,
        PB_SIGMA, PB_CHI2, PB_NPIX, PB_ITERS, PB_FLAG, PB_NEPOCHS, PB_SUMMARY, PB_STATUS, PB_COUNT };
 
-struct celeste_phot_ctx {
-    celeste_ctx_t *c = nullptr;
-    PhotBuf buf[PB_COUNT];
+struct celeste_phot_ctx : ClientCtx<PB_COUNT, 5, 4> {
     // host staging of one call: kept here so that it outlives the asynchronous copies
-    std::vector<PhotItem> items;
+    std::vector<VisitItem> items;
     std::vector<PhotEntry> entries;
     std::vector<int32_t> list;         // the entries solved from LDS, class by class, then the streamed ones
     std::vector<int64_t> eoff;
-    hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-    float last_ms[4] = {0, 0, 0, 0};
 };
-
-template <class T>
-static hipError_t phot_get(celeste_phot_ctx_t *f, int k, size_t bytes, T **out) {
-    PhotBuf &s = f->buf[k];
-    if (bytes > s.cap) {
-        hipError_t e = hipStreamSynchronize(f->c->stream);
-        if (e != hipSuccess) return e;
-        if (s.p) { (void)hipFree(s.p); s.p = nullptr; s.cap = 0; }
-        const size_t cap = std::max<size_t>(bytes, 256);
-        e = hipMalloc(&s.p, cap);
-        if (e != hipSuccess) return e;
-        s.cap = cap;
-    }
-    *out = (T *)s.p;
-    return hipSuccess;
-}
 
 extern "C" int celeste_phot_version(void) { return CELESTE_PHOT_ABI_VERSION; }
 
 extern "C" const char *celeste_phot_strerror(int status) { return celeste_strerror(status); }
 
-// The context's stream comes from the engine's pool (celeste_ctx_create: stream_acquire) and goes back to it
-// (celeste_ctx_destroy: stream_retire); no stream is created or destroyed per call.
 extern "C" int celeste_phot_ctx_create(const celeste_problem_t *problem, int device, celeste_phot_ctx_t **out) try {
-    if (!out) return CELESTE_ERR_INVALID_ARG;
-    *out = nullptr;
-    celeste_ctx_t *c = nullptr;
-    const int rc = celeste_ctx_create(problem, device, &c);
+    const int rc = client_create(problem, device, out);
     if (rc != CELESTE_OK) return rc;
-    celeste_phot_ctx_t *f = new celeste_phot_ctx_t();
-    f->c = c;
-    for (auto &e : f->ev)
-        if (hipEventCreate(&e) != hipSuccess) { celeste_phot_ctx_destroy(f); return CELESTE_ERR_HIP; }
     // the LDS path declares more than the 64 KiB a launch gets without asking
     if (hipFuncSetAttribute(reinterpret_cast<const void *>(&phot_solve_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            CELESTE_PHOT_LDS_PIXELS * 24) != hipSuccess) { celeste_phot_ctx_destroy(f); return CELESTE_ERR_HIP; }
-    *out = f;
+                            CELESTE_PHOT_LDS_PIXELS * 24) != hipSuccess) {
+        client_destroy(*out);
+        *out = nullptr;
+        return CELESTE_ERR_HIP;
+    }
     return CELESTE_OK;
 } ABI_CATCH
 
-extern "C" void celeste_phot_ctx_destroy(celeste_phot_ctx_t *f) {
-    if (!f) return;
-    if (f->c) {
-        (void)hipSetDevice(f->c->device);
-        (void)hipStreamSynchronize(f->c->stream);
-        for (auto &s : f->buf) if (s.p) (void)hipFree(s.p);
-        for (auto &e : f->ev) if (e) (void)hipEventDestroy(e);
-        celeste_ctx_destroy(f->c);
-    }
-    delete f;
-}
+extern "C" void celeste_phot_ctx_destroy(celeste_phot_ctx_t *f) { client_destroy(f); }
 
 extern "C" int celeste_phot_light_curves(celeste_phot_ctx_t *f, const double *vp, int32_t n_targets, const int32_t *targets,
                                          const celeste_phot_params_t *params, int64_t *entry_offsets, int32_t *image,
@@ -404,41 +303,26 @@ extern "C" int celeste_phot_light_curves(celeste_phot_ctx_t *f, const double *vp
     if (!(pr.tol_sigma > 0.0 && std::isfinite(pr.tol_sigma)) || pr.max_iters < 1 || pr.lds_max_pixels < 0)
         return CELESTE_ERR_INVALID_ARG;
     celeste_ctx_t *c = f->c;
-    for (int ti = 0; ti < n_targets; ++ti)
-        if (targets[ti] < 0 || targets[ti] >= c->S) return CELESTE_ERR_INVALID_ARG;
+    if (!client_targets_ok(c, n_targets, targets)) return CELESTE_ERR_INVALID_ARG;
     if (n_targets == 0) return CELESTE_OK;
     const int lds_cap = pr.lds_max_pixels > 0 ? std::min<int>(pr.lds_max_pixels, CELESTE_PHOT_LDS_PIXELS) : CELESTE_PHOT_LDS_PIXELS;
-    // the work list: (visit of a target, chunk) in (target, image, chunk) order; the entries in (target, image) order
-    std::vector<PhotItem> &items = f->items;
+    // the work list, and the entries in (target, image) order: eoff[ti] .. eoff[ti + 1] are target ti's
+    std::vector<VisitItem> &items = f->items;
     std::vector<PhotEntry> &entries = f->entries;
     std::vector<int64_t> &eoff = f->eoff;
-    items.clear();
     entries.clear();
     eoff.assign((size_t)n_targets + 1, 0);
-    const int chunk = c->chunk_px;       // (a multiple of 64)
     int64_t n_tiles = 0, poff = 0;
-    for (int ti = 0; ti < n_targets; ++ti) {
-        const int t = targets[ti];
-        eoff[ti] = (int64_t)entries.size();
-        for (int v = c->h_vis_off[t]; v < c->h_vis_off[t + 1]; ++v) {
-            const DevPatch &P = c->h_patches[v];
-            const int npx = P.H2 * P.W2;
-            if (npx <= 0) continue;      // (every image is listed when the table is dense: an empty patch is no entry)
-            if (entries.size() >= 0x7fffff00ull) return CELESTE_ERR_INVALID_ARG;
+    if (!client_walk(c, n_targets, targets, items, n_tiles, poff, [&](int ti, int v, int npx, int64_t tile0, int64_t, int64_t px_off) {
+            if (entries.size() >= 0x7fffff00ull) return false;
             PhotEntry E;
-            E.px_off = poff; E.npx = npx; E.tile0 = (int32_t)n_tiles; E.n = c->h_vis_img[v]; E.ti = ti; E.pad[0] = E.pad[1] = 0;
+            E.px_off = px_off; E.npx = npx; E.tile0 = (int32_t)tile0; E.n = c->h_vis_img[v]; E.ti = ti; E.pad[0] = E.pad[1] = 0;
             entries.push_back(E);
-            for (int p0 = 0; p0 < npx; p0 += chunk) {
-                if (n_tiles > 0x7fffff00ll || items.size() >= 0x7fffff00ull) return CELESTE_ERR_INVALID_ARG;   // (32-bit tile and grid indices)
-                PhotItem it;
-                it.sn = v; it.n = E.n; it.p0 = p0; it.tile0 = (int32_t)n_tiles; it.px_off = poff;
-                items.push_back(it);
-                n_tiles += (std::min(npx, p0 + chunk) - p0 + 63) / 64;
-            }
-            poff += npx;
-        }
-    }
-    eoff[n_targets] = (int64_t)entries.size();
+            ++eoff[ti + 1];
+            return true;
+        })) return CELESTE_ERR_INVALID_ARG;
+    for (int ti = 0; ti < n_targets; ++ti) eoff[ti + 1] += eoff[ti];
+    const int chunk = c->chunk_px;
     const size_t nt = (size_t)n_targets, ni = items.size(), ne = entries.size();
     // the solve lists: the entries solved from LDS by size class, one launch per class -- a launch declares the LDS of its
     // largest patch for every workgroup, and the classes end where another workgroup fits a CU's 160 KiB (6, 3, 2, 1 per CU)
@@ -462,48 +346,45 @@ extern "C" int celeste_phot_light_curves(celeste_phot_ctx_t *f, const double *vp
     HIP_TRY(hipSetDevice(c->device));
     double *d_vp = nullptr, *d_sa = nullptr, *d_sb = nullptr, *d_sx = nullptr, *d_alpha = nullptr, *d_sigma = nullptr,
            *d_chi2 = nullptr, *d_summary = nullptr;
-    PhotItem *d_items = nullptr;
+    VisitItem *d_items = nullptr;
     PhotEntry *d_entries = nullptr;
     PhotTileInfo *d_info = nullptr;
     int64_t *d_eoff = nullptr;
     int32_t *d_list = nullptr, *d_targets = nullptr, *d_image = nullptr, *d_band = nullptr, *d_npix = nullptr, *d_iters = nullptr,
             *d_flag = nullptr, *d_nepochs = nullptr, *d_status = nullptr;
     const size_t npl = (size_t)poff * sizeof(double);
-    if (phot_get(f, PB_VP, (size_t)c->S * CEL_P * sizeof(double), &d_vp) != hipSuccess ||
-        phot_get(f, PB_ITEMS, ni * sizeof(PhotItem), &d_items) != hipSuccess ||
-        phot_get(f, PB_ENTRIES, ne * sizeof(PhotEntry), &d_entries) != hipSuccess ||
-        phot_get(f, PB_INFO, (size_t)n_tiles * sizeof(PhotTileInfo), &d_info) != hipSuccess ||
-        phot_get(f, PB_SA, npl, &d_sa) != hipSuccess || phot_get(f, PB_SB, npl, &d_sb) != hipSuccess ||
-        phot_get(f, PB_SX, npl, &d_sx) != hipSuccess ||
-        phot_get(f, PB_LIST, ne * sizeof(int32_t), &d_list) != hipSuccess ||
-        phot_get(f, PB_TARGETS, nt * sizeof(int32_t), &d_targets) != hipSuccess ||
-        phot_get(f, PB_EOFF, (nt + 1) * sizeof(int64_t), &d_eoff) != hipSuccess ||
-        phot_get(f, PB_IMAGE, ne * sizeof(int32_t), &d_image) != hipSuccess ||
-        phot_get(f, PB_BAND, ne * sizeof(int32_t), &d_band) != hipSuccess ||
-        phot_get(f, PB_ALPHA, ne * sizeof(double), &d_alpha) != hipSuccess ||
-        phot_get(f, PB_SIGMA, ne * sizeof(double), &d_sigma) != hipSuccess ||
-        phot_get(f, PB_CHI2, ne * sizeof(double), &d_chi2) != hipSuccess ||
-        phot_get(f, PB_NPIX, ne * sizeof(int32_t), &d_npix) != hipSuccess ||
-        phot_get(f, PB_ITERS, ne * sizeof(int32_t), &d_iters) != hipSuccess ||
-        phot_get(f, PB_FLAG, ne * sizeof(int32_t), &d_flag) != hipSuccess ||
-        phot_get(f, PB_NEPOCHS, nt * PHOT_NB * sizeof(int32_t), &d_nepochs) != hipSuccess ||
-        phot_get(f, PB_SUMMARY, nt * PHOT_NB * PHOT_NSUM * sizeof(double), &d_summary) != hipSuccess ||
-        phot_get(f, PB_STATUS, nt * sizeof(int32_t), &d_status) != hipSuccess)
+    if (client_get(f, PB_VP, (size_t)c->S * CEL_P * sizeof(double), &d_vp) != hipSuccess ||
+        client_get(f, PB_ITEMS, ni * sizeof(VisitItem), &d_items) != hipSuccess ||
+        client_get(f, PB_ENTRIES, ne * sizeof(PhotEntry), &d_entries) != hipSuccess ||
+        client_get(f, PB_INFO, (size_t)n_tiles * sizeof(PhotTileInfo), &d_info) != hipSuccess ||
+        client_get(f, PB_SA, npl, &d_sa) != hipSuccess || client_get(f, PB_SB, npl, &d_sb) != hipSuccess ||
+        client_get(f, PB_SX, npl, &d_sx) != hipSuccess ||
+        client_get(f, PB_LIST, ne * sizeof(int32_t), &d_list) != hipSuccess ||
+        client_get(f, PB_TARGETS, nt * sizeof(int32_t), &d_targets) != hipSuccess ||
+        client_get(f, PB_EOFF, (nt + 1) * sizeof(int64_t), &d_eoff) != hipSuccess ||
+        client_get(f, PB_IMAGE, ne * sizeof(int32_t), &d_image) != hipSuccess ||
+        client_get(f, PB_BAND, ne * sizeof(int32_t), &d_band) != hipSuccess ||
+        client_get(f, PB_ALPHA, ne * sizeof(double), &d_alpha) != hipSuccess ||
+        client_get(f, PB_SIGMA, ne * sizeof(double), &d_sigma) != hipSuccess ||
+        client_get(f, PB_CHI2, ne * sizeof(double), &d_chi2) != hipSuccess ||
+        client_get(f, PB_NPIX, ne * sizeof(int32_t), &d_npix) != hipSuccess ||
+        client_get(f, PB_ITERS, ne * sizeof(int32_t), &d_iters) != hipSuccess ||
+        client_get(f, PB_FLAG, ne * sizeof(int32_t), &d_flag) != hipSuccess ||
+        client_get(f, PB_NEPOCHS, nt * PHOT_NB * sizeof(int32_t), &d_nepochs) != hipSuccess ||
+        client_get(f, PB_SUMMARY, nt * PHOT_NB * PHOT_NSUM * sizeof(double), &d_summary) != hipSuccess ||
+        client_get(f, PB_STATUS, nt * sizeof(int32_t), &d_status) != hipSuccess)
         return CELESTE_ERR_HIP;
     hipStream_t st = c->stream;
     HIP_TRY(hipMemcpyAsync(d_vp, vp, (size_t)c->S * CEL_P * sizeof(double), hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(d_targets, targets, nt * sizeof(int32_t), hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(d_eoff, eoff.data(), (nt + 1) * sizeof(int64_t), hipMemcpyHostToDevice, st));
-    if (ni > 0) HIP_TRY(hipMemcpyAsync(d_items, items.data(), ni * sizeof(PhotItem), hipMemcpyHostToDevice, st));
+    if (ni > 0) HIP_TRY(hipMemcpyAsync(d_items, items.data(), ni * sizeof(VisitItem), hipMemcpyHostToDevice, st));
     if (ne > 0) {
         HIP_TRY(hipMemcpyAsync(d_entries, entries.data(), ne * sizeof(PhotEntry), hipMemcpyHostToDevice, st));
         HIP_TRY(hipMemcpyAsync(d_list, list.data(), ne * sizeof(int32_t), hipMemcpyHostToDevice, st));
     }
     HIP_TRY(hipEventRecord(f->ev[0], st));
-    if (c->V > 0)
-        hipLaunchKernelGGL(prep_kernel, dim3((unsigned)c->V), dim3(64), 0, st, d_vp, c->d_images, c->d_patches, c->d_vis_src,
-                           c->d_vis_img, c->N, c->K, c->d_srcimg, c->d_comps, nullptr, c->d_vis_off, c->M, (int)c->dense, nullptr,
-                           nullptr, 0);
+    client_launch_prep(c, d_vp, st);
     HIP_TRY(hipEventRecord(f->ev[1], st));
     if (ni > 0)
         hipLaunchKernelGGL(phot_pixel_kernel, dim3((unsigned)ni), dim3(64), 0, st, d_items, c->d_images, c->d_patches, c->d_coefs,
@@ -539,14 +420,8 @@ extern "C" int celeste_phot_light_curves(celeste_phot_ctx_t *f, const double *vp
     HIP_TRY(hipMemcpyAsync(summary, d_summary, nt * PHOT_NB * PHOT_NSUM * sizeof(double), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipMemcpyAsync(status, d_status, nt * sizeof(int32_t), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
-    for (int k = 0; k < 4; ++k)
-        if (hipEventElapsedTime(&f->last_ms[k], f->ev[k], f->ev[k + 1]) != hipSuccess) f->last_ms[k] = 0;
-    for (int ti = 0; ti < n_targets; ++ti) if (status[ti] != CELESTE_OK) return status[ti];
-    return CELESTE_OK;
+    client_stage_ms(f);
+    return client_first_status(status, n_targets);
 } ABI_CATCH
 
-extern "C" int celeste_phot_last_ms(celeste_phot_ctx_t *f, float ms[4]) {
-    if (!f || !ms) return CELESTE_ERR_INVALID_ARG;
-    for (int k = 0; k < 4; ++k) ms[k] = f->last_ms[k];
-    return CELESTE_OK;
-}
+extern "C" int celeste_phot_last_ms(celeste_phot_ctx_t *f, float ms[4]) { return client_last_ms(f, ms); }

@@ -12,6 +12,7 @@ from typing import List, Optional, Sequence
 
 import numpy as np
 
+from . import _binding
 from .model import Image, ImagePatch, PatchRow, box_around_point, clamp_box, julia_round
 from .params import CatalogEntry
 
@@ -60,30 +61,10 @@ class DetectError(RuntimeError):
         self.status = status
 
 
-_lib = None
+_check = _binding.checker("detect", DetectError)
 
 
-def load_library(path: Optional[str] = None) -> C.CDLL:
-    """The detection library; CELESTE_MI355X_DETECT_LIB overrides its path.  Like cabi.load_library, torch's HIP runtime
-    is loaded first so that one runtime serves the process."""
-    global _lib
-    if _lib is not None and path is None:
-        return _lib
-    path = path or os.environ.get("CELESTE_MI355X_DETECT_LIB") or LIB_PATH
-    if not os.path.exists(path):
-        raise ImportError("HIP extension %s is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
-                          "(hipcc --offload-arch=gfx950). There is no CPU fallback." % path)
-    try:
-        import torch  # noqa: F401
-        if torch.cuda.is_available():
-            torch.cuda.init()
-    except (ImportError, RuntimeError):
-        pass
-    lib = C.CDLL(path)
-    lib.celeste_detect_version.restype = C.c_int
-    if lib.celeste_detect_version() // 100 != ABI_VERSION // 100:
-        raise ImportError("%s has ABI version %d, this binding was written against %d" % (path, lib.celeste_detect_version(),
-                                                                                           ABI_VERSION))
+def _declare(lib):
     lib.celeste_detect_strerror.restype = C.c_char_p
     lib.celeste_detect_strerror.argtypes = [C.c_int]
     lib.celeste_detect_run.restype = C.c_int
@@ -91,9 +72,13 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
                                        C.POINTER(C.POINTER(ResultT))]
     lib.celeste_detect_result_free.restype = None
     lib.celeste_detect_result_free.argtypes = [C.POINTER(ResultT)]
-    if path == LIB_PATH or path == os.environ.get("CELESTE_MI355X_DETECT_LIB"):
-        _lib = lib
-    return lib
+
+
+def load_library(path: Optional[str] = None) -> C.CDLL:
+    """The detection library; CELESTE_MI355X_DETECT_LIB overrides its path (_binding.open_library).  It does not need the
+    engine's library: torch's HIP runtime alone is loaded first, so that one runtime serves the process."""
+    return _binding.open_library("detect", LIB_PATH, "CELESTE_MI355X_DETECT_LIB", ABI_VERSION, "celeste_detect_version", _declare,
+                                 path, engine=False)
 
 
 @dataclass
@@ -158,8 +143,7 @@ def extract(images, device: int = 0, thresh: float = 1.3, minarea: int = 5, debl
                   deblend_cont, lds_max_pixels, 0)
     res = C.POINTER(ResultT)()
     st = lib.celeste_detect_run(device, len(images), arr, C.byref(prm), C.byref(res))
-    if st != OK:
-        raise DetectError(st, lib.celeste_detect_strerror(st).decode())
+    _check(lib, st)
     try:
         out = []
         if stage_ms is not None:

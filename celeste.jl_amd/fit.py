@@ -17,7 +17,7 @@ from typing import List, Optional, Sequence
 
 import numpy as np
 
-from . import cabi
+from . import _binding, cabi
 from .cabi import P
 
 LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc", "fit", "libceleste_fit.so")
@@ -28,25 +28,12 @@ CHI2, RESID, OWN, SELF, WRES, WINFO, MAX_Z = range(NSTATS)
 EXPORTED_SYMBOLS = ["celeste_fit_version", "celeste_fit_strerror", "celeste_fit_ctx_create", "celeste_fit_ctx_destroy",
                     "celeste_fit_stats", "celeste_fit_last_ms"]
 
-_lib = None
 _dp, _ip, _lp = cabi.c_double_p, cabi.c_int32_p, cabi.c_int64_p
+_ptr = _binding.ptr
+_check = _binding.checker("fit")
 
 
-def load_library(path: Optional[str] = None) -> C.CDLL:
-    """libceleste_fit.so; CELESTE_MI355X_FIT_LIB overrides its path.  torch's HIP runtime is loaded first (cabi)."""
-    global _lib
-    if _lib is not None and path is None:
-        return _lib
-    path = path or os.environ.get("CELESTE_MI355X_FIT_LIB") or LIB_PATH
-    if not os.path.exists(path):
-        raise ImportError("HIP extension %s is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
-                          "(hipcc --offload-arch=gfx950). There is no CPU fallback." % path)
-    cabi.load_library()
-    lib = C.CDLL(path)
-    lib.celeste_fit_version.restype = C.c_int
-    if lib.celeste_fit_version() // 100 != ABI_VERSION // 100:
-        raise ImportError("%s has ABI version %d, this binding was written against %d" % (path, lib.celeste_fit_version(),
-                                                                                           ABI_VERSION))
+def _declare(lib):
     vp = C.c_void_p
     lib.celeste_fit_strerror.restype = C.c_char_p
     lib.celeste_fit_strerror.argtypes = [C.c_int]
@@ -55,17 +42,11 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.celeste_fit_ctx_destroy.restype = None
     lib.celeste_fit_stats.argtypes = [vp, _dp, C.c_int32, _ip, _lp, _dp, _ip, _lp, _dp]
     lib.celeste_fit_last_ms.argtypes = [vp, C.POINTER(C.c_float)]
-    _lib = lib
-    return lib
 
 
-def _check(lib, st: int):
-    if st != 0:
-        raise RuntimeError("libceleste_fit: %s (status %d)" % (lib.celeste_fit_strerror(st).decode(), st))
-
-
-def _ptr(a, t):
-    return None if a is None else a.ctypes.data_as(t)
+def load_library(path: Optional[str] = None) -> C.CDLL:
+    """libceleste_fit.so; CELESTE_MI355X_FIT_LIB overrides its path (_binding.open_library)"""
+    return _binding.open_library("fit", LIB_PATH, "CELESTE_MI355X_FIT_LIB", ABI_VERSION, "celeste_fit_version", _declare, path)
 
 
 def _ratio(num, den):
@@ -131,39 +112,13 @@ def patch_shapes(problem: "cabi.Problem") -> List[list]:
     return out
 
 
-class FitContext:
+class FitContext(_binding.Context):
     """The fit library's copy of a problem (celeste_fit_ctx_t), built from a marshalled celeste_problem_t."""
+    _name, _load = "fit", staticmethod(load_library)
 
     def __init__(self, problem: "cabi.Problem", device: int = 0):
-        self.lib = load_library()
-        self.problem = problem
-        self.S = problem.n_sources
-        self._keep: list = []
-        pc = cabi.ProblemT.from_buffer_copy(problem.c)
-        if not pc.images:
-            pc.images = cabi.marshal_image_structs(problem.images, self._keep)
-        self._pc = pc
+        super().__init__(problem, device)
         self._shapes = None
-        h = C.c_void_p()
-        _check(self.lib, self.lib.celeste_fit_ctx_create(C.byref(pc), int(device), C.byref(h)))
-        self.handle = h
-
-    def close(self):
-        if getattr(self, "handle", None):
-            self.lib.celeste_fit_ctx_destroy(self.handle)
-            self.handle = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def stats(self, vp, targets: Sequence[int], stamps: bool = False) -> FitStats:
         """celeste_fit_stats at the table vp [S, 44] for `targets` (repeats allowed).  A target whose parameters or expected

@@ -23,7 +23,7 @@ from typing import Dict, List, Optional, Sequence
 
 import numpy as np
 
-from . import cabi
+from . import _binding, cabi
 
 LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc", "mcmc", "libceleste_mcmc.so")
 ABI_VERSION = 100          # CELESTE_MCMC_ABI_VERSION of include/celeste_mcmc.h
@@ -212,24 +212,7 @@ def consolidate_samples(summary: Dict[str, Dict[str, float]]) -> Dict[str, float
 
 
 # ---- the library ----------------------------------------------------------------------------------------------------
-_lib = None
-
-
-def load_library(path: Optional[str] = None) -> C.CDLL:
-    """libceleste_mcmc.so; CELESTE_MI355X_MCMC_LIB overrides its path.  torch's HIP runtime is loaded first (cabi)."""
-    global _lib
-    if _lib is not None and path is None:
-        return _lib
-    path = path or os.environ.get("CELESTE_MI355X_MCMC_LIB") or LIB_PATH
-    if not os.path.exists(path):
-        raise ImportError("HIP extension %s is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
-                          "(hipcc --offload-arch=gfx950). There is no CPU fallback." % path)
-    cabi.load_library()
-    lib = C.CDLL(path)
-    lib.celeste_mcmc_version.restype = C.c_int
-    if lib.celeste_mcmc_version() // 100 != ABI_VERSION // 100:
-        raise ImportError("%s has ABI version %d, this binding was written against %d" % (path, lib.celeste_mcmc_version(),
-                                                                                           ABI_VERSION))
+def _declare(lib):
     vp, dp, ip = C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_int32)
     lib.celeste_mcmc_strerror.restype = C.c_char_p
     lib.celeste_mcmc_strerror.argtypes = [C.c_int]
@@ -244,22 +227,22 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
                                      C.POINTER(C.c_int64), ip]
     lib.celeste_mcmc_last_ms.restype = C.c_int
     lib.celeste_mcmc_last_ms.argtypes = [vp, C.POINTER(C.c_float)]
-    if path == LIB_PATH or path == os.environ.get("CELESTE_MI355X_MCMC_LIB"):
-        _lib = lib
-    return lib
+
+
+def load_library(path: Optional[str] = None) -> C.CDLL:
+    """libceleste_mcmc.so; CELESTE_MI355X_MCMC_LIB overrides its path (_binding.open_library)"""
+    return _binding.open_library("mcmc", LIB_PATH, "CELESTE_MI355X_MCMC_LIB", ABI_VERSION, "celeste_mcmc_version", _declare, path)
 
 
 def _dp(a: np.ndarray):
-    return a.ctypes.data_as(C.POINTER(C.c_double))
+    return _binding.ptr(a, C.POINTER(C.c_double))
 
 
 def _ip(a: np.ndarray):
-    return a.ctypes.data_as(C.POINTER(C.c_int32))
+    return _binding.ptr(a, C.POINTER(C.c_int32))
 
 
-def _check(lib, st: int):
-    if st != 0:
-        raise RuntimeError("libceleste_mcmc: %s (status %d)" % (lib.celeste_mcmc_strerror(st).decode(), st))
+_check = _binding.checker("mcmc")
 
 
 def source_table(catalog) -> "C.Array":
@@ -275,31 +258,9 @@ def source_table(catalog) -> "C.Array":
     return arr
 
 
-class MCMCContext:
+class MCMCContext(_binding.Context):
     """The device copy of a problem for MCMC (celeste_mcmc_ctx_t), built from a marshalled celeste_problem_t."""
-
-    def __init__(self, problem: "cabi.Problem", device: int = 0):
-        self.lib = load_library()
-        self.problem = problem
-        self._keep: list = []
-        pc = cabi.ProblemT.from_buffer_copy(problem.c)
-        if not pc.images:
-            pc.images = cabi.marshal_image_structs(problem.images, self._keep)
-        self._pc = pc
-        h = C.c_void_p()
-        _check(self.lib, self.lib.celeste_mcmc_ctx_create(C.byref(pc), int(device), C.byref(h)))
-        self.handle = h
-
-    def close(self):
-        if getattr(self, "handle", None):
-            self.lib.celeste_mcmc_ctx_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+    _name, _load = "mcmc", staticmethod(load_library)
 
     def loglike(self, catalog, targets: Sequence[int], boxes: np.ndarray, model: int, which: Sequence[int], theta: np.ndarray):
         """celeste_mcmc_loglike: (ll, lp) of the points theta[k] (7 or 11 entries) of targets[which[k]]"""

@@ -17,7 +17,7 @@ from typing import Optional, Sequence
 
 import numpy as np
 
-from . import cabi
+from . import _binding, cabi
 from .cabi import P
 
 LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc", "phot", "libceleste_phot.so")
@@ -30,8 +30,9 @@ WMEAN, WMEAN_SIGMA, CHI2_VAR = range(NSUMMARY)
 EXPORTED_SYMBOLS = ["celeste_phot_version", "celeste_phot_strerror", "celeste_phot_ctx_create", "celeste_phot_ctx_destroy",
                     "celeste_phot_light_curves", "celeste_phot_last_ms"]
 
-_lib = None
 _dp, _ip, _lp = cabi.c_double_p, cabi.c_int32_p, cabi.c_int64_p
+_ptr = _binding.ptr
+_check = _binding.checker("phot")
 
 
 class ParamsT(C.Structure):
@@ -39,21 +40,7 @@ class ParamsT(C.Structure):
     _fields_ = [("tol_sigma", C.c_double), ("max_iters", C.c_int32), ("lds_max_pixels", C.c_int32)]
 
 
-def load_library(path: Optional[str] = None) -> C.CDLL:
-    """libceleste_phot.so; CELESTE_MI355X_PHOT_LIB overrides its path.  torch's HIP runtime is loaded first (cabi)."""
-    global _lib
-    if _lib is not None and path is None:
-        return _lib
-    path = path or os.environ.get("CELESTE_MI355X_PHOT_LIB") or LIB_PATH
-    if not os.path.exists(path):
-        raise ImportError("HIP extension %s is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
-                          "(hipcc --offload-arch=gfx950). There is no CPU fallback." % path)
-    cabi.load_library()
-    lib = C.CDLL(path)
-    lib.celeste_phot_version.restype = C.c_int
-    if lib.celeste_phot_version() // 100 != ABI_VERSION // 100:
-        raise ImportError("%s has ABI version %d, this binding was written against %d" % (path, lib.celeste_phot_version(),
-                                                                                           ABI_VERSION))
+def _declare(lib):
     vp = C.c_void_p
     lib.celeste_phot_strerror.restype = C.c_char_p
     lib.celeste_phot_strerror.argtypes = [C.c_int]
@@ -63,17 +50,11 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.celeste_phot_light_curves.argtypes = [vp, _dp, C.c_int32, _ip, C.POINTER(ParamsT), _lp, _ip, _dp, _dp, _dp, _ip, _ip, _ip,
                                               _ip, _dp, _ip]
     lib.celeste_phot_last_ms.argtypes = [vp, C.POINTER(C.c_float)]
-    _lib = lib
-    return lib
 
 
-def _check(lib, st: int):
-    if st != 0:
-        raise RuntimeError("libceleste_phot: %s (status %d)" % (lib.celeste_phot_strerror(st).decode(), st))
-
-
-def _ptr(a, t):
-    return None if a is None else a.ctypes.data_as(t)
+def load_library(path: Optional[str] = None) -> C.CDLL:
+    """libceleste_phot.so; CELESTE_MI355X_PHOT_LIB overrides its path (_binding.open_library)"""
+    return _binding.open_library("phot", LIB_PATH, "CELESTE_MI355X_PHOT_LIB", ABI_VERSION, "celeste_phot_version", _declare, path)
 
 
 def expected_band_flux(vp) -> np.ndarray:
@@ -180,40 +161,14 @@ def entry_counts(problem: "cabi.Problem") -> np.ndarray:
     return np.bincount(np.asarray(src)[ok], minlength=S).astype(np.int64)
 
 
-class PhotContext:
+class PhotContext(_binding.Context):
     """The photometry library's copy of a problem (celeste_phot_ctx_t), built from a marshalled celeste_problem_t."""
+    _name, _load = "phot", staticmethod(load_library)
 
     def __init__(self, problem: "cabi.Problem", device: int = 0):
-        self.lib = load_library()
-        self.problem = problem
-        self.S = problem.n_sources
-        self._keep: list = []
-        pc = cabi.ProblemT.from_buffer_copy(problem.c)
-        if not pc.images:
-            pc.images = cabi.marshal_image_structs(problem.images, self._keep)
-        self._pc = pc
+        super().__init__(problem, device)
         self._counts = None
         self._bands = np.array([im.b - 1 for im in problem.images], dtype=np.int32)
-        h = C.c_void_p()
-        _check(self.lib, self.lib.celeste_phot_ctx_create(C.byref(pc), int(device), C.byref(h)))
-        self.handle = h
-
-    def close(self):
-        if getattr(self, "handle", None):
-            self.lib.celeste_phot_ctx_destroy(self.handle)
-            self.handle = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def light_curves(self, vp, targets: Sequence[int], tol_sigma: float = 1e-9, max_iters: int = 50,
                      lds_max_pixels: int = 0) -> LightCurves:

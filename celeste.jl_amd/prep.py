@@ -22,7 +22,7 @@ from typing import List, Optional, Sequence
 
 import numpy as np
 
-from . import cabi
+from . import _binding, cabi
 from .model import PatchTable, SDSSPSFMap, get_psf_width
 from .params import CatalogEntry
 
@@ -109,24 +109,7 @@ class PrepError(RuntimeError):
         self.status = status
 
 
-_lib = None
-
-
-def load_library(path: Optional[str] = None) -> C.CDLL:
-    """libceleste_prep.so; CELESTE_MI355X_PREP_LIB overrides its path.  torch's HIP runtime is loaded first (cabi)."""
-    global _lib
-    if _lib is not None and path is None:
-        return _lib
-    path = path or os.environ.get("CELESTE_MI355X_PREP_LIB") or LIB_PATH
-    if not os.path.exists(path):
-        raise ImportError("HIP extension %s is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
-                          "(hipcc --offload-arch=gfx950). There is no CPU fallback." % path)
-    cabi.load_library()
-    lib = C.CDLL(path)
-    lib.celeste_prep_version.restype = C.c_int
-    if lib.celeste_prep_version() // 100 != ABI_VERSION // 100:
-        raise ImportError("%s has ABI version %d, this binding was written against %d" % (path, lib.celeste_prep_version(),
-                                                                                           ABI_VERSION))
+def _declare(lib):
     assert SOURCE_DTYPE.itemsize == C.sizeof(PrepSourceT) and DETECTION_DTYPE.itemsize == C.sizeof(PrepDetectionT)
     vp = C.c_void_p
     lib.celeste_prep_strerror.restype = C.c_char_p
@@ -159,14 +142,14 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.celeste_prep_images_set_wcs.argtypes = [vp, C.c_int32, C.POINTER(PrepWcsT)]
     lib.celeste_prep_result_get_jacobians.restype = C.c_int
     lib.celeste_prep_result_get_jacobians.argtypes = [vp, C.POINTER(c_double_p)]
-    if path == LIB_PATH or path == os.environ.get("CELESTE_MI355X_PREP_LIB"):
-        _lib = lib
-    return lib
 
 
-def _check(lib, st: int):
-    if st != 0:
-        raise PrepError(st, lib.celeste_prep_strerror(st).decode())
+def load_library(path: Optional[str] = None) -> C.CDLL:
+    """libceleste_prep.so; CELESTE_MI355X_PREP_LIB overrides its path (_binding.open_library)"""
+    return _binding.open_library("prep", LIB_PATH, "CELESTE_MI355X_PREP_LIB", ABI_VERSION, "celeste_prep_version", _declare, path)
+
+
+_check = _binding.checker("prep", PrepError)
 
 
 def last_ms() -> dict:

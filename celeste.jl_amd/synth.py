@@ -21,7 +21,7 @@ from typing import List, Optional, Sequence
 
 import numpy as np
 
-from . import cabi
+from . import _binding, cabi
 from .model import ConstantPSFMap, SDSSPSFMap
 
 LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc", "synth", "libceleste_synth.so")
@@ -52,24 +52,7 @@ class SynthError(RuntimeError):
         self.status = status
 
 
-_lib = None
-
-
-def load_library(path: Optional[str] = None) -> C.CDLL:
-    """libceleste_synth.so; CELESTE_MI355X_SYNTH_LIB overrides its path.  torch's HIP runtime is loaded first (cabi)."""
-    global _lib
-    if _lib is not None and path is None:
-        return _lib
-    path = path or os.environ.get("CELESTE_MI355X_SYNTH_LIB") or LIB_PATH
-    if not os.path.exists(path):
-        raise ImportError("HIP extension %s is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
-                          "(hipcc --offload-arch=gfx950). There is no CPU fallback." % path)
-    cabi.load_library()
-    lib = C.CDLL(path)
-    lib.celeste_synth_version.restype = C.c_int
-    if lib.celeste_synth_version() // 100 != ABI_VERSION // 100:
-        raise ImportError("%s has ABI version %d, this binding was written against %d" % (path, lib.celeste_synth_version(),
-                                                                                           ABI_VERSION))
+def _declare(lib):
     lib.celeste_synth_strerror.restype = C.c_char_p
     lib.celeste_synth_strerror.argtypes = [C.c_int]
     lib.celeste_synth_generate.restype = C.c_int
@@ -80,14 +63,14 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
                                          C.POINTER(C.c_float), C.POINTER(C.c_int64)]
     lib.celeste_synth_last_ms.restype = C.c_int
     lib.celeste_synth_last_ms.argtypes = [C.POINTER(C.c_float)]
-    if path == LIB_PATH or path == os.environ.get("CELESTE_MI355X_SYNTH_LIB"):
-        _lib = lib
-    return lib
 
 
-def _check(lib, st: int):
-    if st != 0:
-        raise SynthError(st, lib.celeste_synth_strerror(st).decode())
+def load_library(path: Optional[str] = None) -> C.CDLL:
+    """libceleste_synth.so; CELESTE_MI355X_SYNTH_LIB overrides its path (_binding.open_library)"""
+    return _binding.open_library("synth", LIB_PATH, "CELESTE_MI355X_SYNTH_LIB", ABI_VERSION, "celeste_synth_version", _declare, path)
+
+
+_check = _binding.checker("synth", SynthError)
 
 
 def last_ms() -> List[float]:

@@ -31,6 +31,23 @@ def test_the_blend_library_exports_its_c_abi_and_nothing_else(lib):
     assert b"no CPU fallback" in b.celeste_blend_strerror(5)
 
 
+@pytest.mark.parametrize("name", ["blend", "fit", "phot"])
+def test_an_explicit_path_gets_its_own_handle_and_leaves_the_default_alone(lib, name, tmp_path):
+    """load_library(path) opens that file; the handle every context gets from load_library() stays the default path's"""
+    import importlib
+    import shutil
+    mod = importlib.import_module("celeste_jl_amd." + name)
+    copy = str(tmp_path / os.path.basename(mod.LIB_PATH))
+    shutil.copy(mod.LIB_PATH, copy)
+    other = mod.load_library(copy)
+    assert other._name == copy
+    assert getattr(other, "celeste_%s_version" % name)() == mod.ABI_VERSION
+    assert len(getattr(other, "celeste_%s_ctx_create" % name).argtypes) == 3          # (declared like the default handle)
+    default = mod.load_library()
+    assert default._name == os.environ.get("CELESTE_MI355X_%s_LIB" % name.upper(), mod.LIB_PATH)
+    assert mod.load_library() is default and mod.load_library(copy) is not other
+
+
 def test_the_julia_shim_binds_the_header():
     """shim/CelesteMI355XBlend.jl cannot run here (no Julia): every ccall names a prototype of include/celeste_blend.h with
     its argument count, every prototype is bound, and the config mirror lists celeste_optim_config_t's fields in order"""
