@@ -9,6 +9,21 @@
 //           parameter row, and the pixel walk of a work item with the ELBO's neighbour rule (visit_pixel_walk)
 #pragma once
 
+// Mutation testing (tests/test_satellite_mutants.py builds fit and phot with -DCELESTE_CLIENT_MUTANT=k and checks that their
+// parity tests notice; its own macro, because both libraries compile the engine, whose CELESTE_MUTANT numbers keep their
+// meaning).  All in visit_pixel_walk; a mutant changes arithmetic or an index inside the same array, never a bound, a size, a
+// barrier or the control flow around one.  0 = the product;
+//   1 = the target's own light also in its patch's last column (w2 < W2)
+//   2 = a neighbour's light also in the neighbour's last column (b < Q.W2; its bitmap index a + Q.H2 b stays <= Q.H2 Q.W2 - 1)
+//   3 = the neighbour's bitmap is ignored
+//   4 = the target's bitmap is read transposed (w2 + W2 h2 <= W2 - 1 + W2 (H2 - 1) = W2 H2 - 1)
+//   5 = iota indexed by column, clamped to its H entries (img.iota[min(w0, img.H - 1)])
+//   6 = the neighbour's star density uses the target's stamp (P.stamp for Q.stamp: both checked at context creation)
+// Never defined in the shipped build.
+#ifndef CELESTE_CLIENT_MUTANT
+#define CELESTE_CLIENT_MUTANT 0
+#endif
+
 // ---- host: the context --------------------------------------------------------------------------------------------------
 struct ClientBuf { void *p = nullptr; size_t cap = 0; };
 
@@ -222,25 +237,49 @@ __device__ __forceinline__ void visit_pixel_walk(const VisitItem &it, const DevI
         const int h0 = P.off_h + h2, w0 = P.off_w + w2;       // 0-based in the image
         const size_t gi = (size_t)h0 + (size_t)img.H * w0;
         const float xf = img.pixels[gi], skyf = img.sky[gi];
+#if CELESTE_CLIENT_MUTANT == 5
+        const double iota = (double)img.iota[min(w0, img.H - 1)];
+#else
         const double iota = (double)img.iota[h0];
+#endif
         bool valid = inp && !isnan(xf);
+#if CELESTE_CLIENT_MUTANT == 4
+        if (valid && P.bitmap_off >= 0) valid = bitmaps[P.bitmap_off + w2 + (int64_t)W2 * h2] != 0;
+#else
         if (valid && P.bitmap_off >= 0) valid = bitmaps[P.bitmap_off + h2 + (int64_t)H2 * w2] != 0;
+#endif
         const double hh = (double)(h0 + 1), ww = (double)(w0 + 1);
         double m = 0.0;
+#if CELESTE_CLIENT_MUTANT == 1
+        if (valid && w2 < W2) m = visit_light(si, tc, NC, coef, etab, hh, ww);
+#else
         if (valid && w2 < W2 - 1) m = visit_light(si, tc, NC, coef, etab, hh, ww);
+#endif
         double B = 0.0;
         for (int64_t q = nb0; q < nb1; ++q) {
             const int v2 = table_entry(vis_off, vis_img, dense, N, nbr_idx[q], n);
             if (v2 < 0) continue;
             const DevPatch &Q = patches[v2];
             const int a = h0 - Q.off_h, b = w0 - Q.off_w;     // 0-based in the neighbour's patch
+#if CELESTE_CLIENT_MUTANT == 2
+            bool in = valid & (a >= 0) & (a < Q.H2) & (b >= 0) & (b < Q.W2);
+#else
             bool in = valid & (a >= 0) & (a < Q.H2) & (b >= 0) & (b < Q.W2 - 1);
+#endif
+#if CELESTE_CLIENT_MUTANT == 3
+            // (the neighbour's bitmap is not read)
+#else
             if (in && Q.bitmap_off >= 0) in = bitmaps[Q.bitmap_off + a + (int64_t)Q.H2 * b] != 0;
+#endif
             if (!__any(in)) continue;                         // (the workgroup is one wavefront: uniform)
             __syncthreads();
             visit_stage_comps(tq, comps + (size_t)v2 * NC, NC);
             __syncthreads();
+#if CELESTE_CLIENT_MUTANT == 6
+            if (in) B += visit_light(srcimg[v2], tq, NC, coefs + (size_t)P.stamp * (CEL_COEF * CEL_COEF), etab, hh, ww);
+#else
             if (in) B += visit_light(srcimg[v2], tq, NC, coefs + (size_t)Q.stamp * (CEL_COEF * CEL_COEF), etab, hh, ww);
+#endif
         }
         const VisitPixel px = {tile, idx, inp, valid, xf, skyf, iota, m, B};
         tile_fn(img, px);

@@ -15,6 +15,19 @@
 #include "../engine_client.h"
 #include "../../../include/celeste_fit.h"
 
+// Mutation testing (tests/test_satellite_mutants.py builds this library with -DCELESTE_FIT_MUTANT=k and checks that
+// tests/test_gpu_fit.py notices).  A mutant changes arithmetic, or reads fewer records of the same array; never a size, a launch,
+// a barrier or anything that could leave an array.  0 = the product;
+//   1 = SELF ignores B (m / (m + B) becomes 1)
+//   2 = an unvisited pixel's stamp gets lam instead of NaN
+//   3 = fit_reduce_kernel adds MAX_Z instead of taking the maximum
+//   4 = fit_reduce_kernel starts at tr.x + 1 when tr.y > 1: the first tile is dropped (a later start inside [tr.x, tr.x + tr.y))
+//   5 = the tiles' bad flag is not reported: never NONFINITE_RESULT
+// Never defined in the shipped build.
+#ifndef CELESTE_FIT_MUTANT
+#define CELESTE_FIT_MUTANT 0
+#endif
+
 #define FIT_NB CELESTE_FIT_BANDS
 #define FIT_NS CELESTE_FIT_NSTATS
 #define FIT_REC 8                      // doubles of a tile record: the seven statistics, one unused
@@ -49,12 +62,20 @@ fit_pixel_kernel(const VisitItem *__restrict__ items, const DevImage *__restrict
             t[CELESTE_FIT_CHI2] = __dmul_rn(r, r) / lam;
             t[CELESTE_FIT_RESID] = r;
             t[CELESTE_FIT_OWN] = own;
+#if CELESTE_FIT_MUTANT == 1
+            t[CELESTE_FIT_SELF] = m != 0.0 ? __dmul_rn(own, 1.0) : 0.0;
+#else
             t[CELESTE_FIT_SELF] = m != 0.0 ? __dmul_rn(own, m / (m + B)) : 0.0;   // (m / (m + 0) = 1: self = own to the bit without neighbours)
+#endif
             t[CELESTE_FIT_WRES] = __dmul_rn(own, r) / lam;
             t[CELESTE_FIT_WINFO] = __dmul_rn(own, own) / lam;
             t[CELESTE_FIT_MAX_Z] = fabs(r) / sqrt(lam);
         }
+#if CELESTE_FIT_MUTANT == 2
+        if (stamps && inp) stamps[it.px_off + idx] = lam;
+#else
         if (stamps && inp) stamps[it.px_off + idx] = valid ? lam : (double)NAN;
+#endif
 #pragma unroll
         for (int k = 0; k < FIT_NS - 1; ++k) t[k] = wave_sum(t[k]);
         t[CELESTE_FIT_MAX_Z] = wave_max(t[CELESTE_FIT_MAX_Z]);
@@ -86,13 +107,25 @@ fit_reduce_kernel(const int2 *__restrict__ tgt_rec, const int32_t *__restrict__ 
     // (a lane's loads do not depend on the tile's band: the loop is a chain of additions, not of loads)
     const int col = k < FIT_NS ? k : 0;
 #pragma unroll 4
+#if CELESTE_FIT_MUTANT == 4
+    for (int r = tr.x + (tr.y > 1 ? 1 : 0); r < tr.x + tr.y; ++r) {
+#else
     for (int r = tr.x; r < tr.x + tr.y; ++r) {
+#endif
         const FitTileInfo fi = info[r];
         const double x = rec[(size_t)r * FIT_REC + col];
+#if CELESTE_FIT_MUTANT == 5
+        bad |= 0;
+#else
         bad |= fi.bad;
+#endif
         const bool mine = fi.band == b;
         if (k < CELESTE_FIT_MAX_Z) acc = mine ? acc + x : acc;
+#if CELESTE_FIT_MUTANT == 3
+        else if (k == CELESTE_FIT_MAX_Z) acc = mine ? acc + x : acc;
+#else
         else if (k == CELESTE_FIT_MAX_Z) acc = mine ? fmax(acc, x) : acc;
+#endif
         else cnt += mine ? fi.n_pix : 0;
     }
     const double *vs = vp + (size_t)targets[ti] * CEL_P;

@@ -27,6 +27,20 @@
 #include "../host_tables.h"
 #include "../../../include/celeste_mcmc.h"
 
+// Mutation testing (tests/test_satellite_mutants.py builds this library with -DCELESTE_MCMC_MUTANT=k and checks that
+// tests/test_gpu_mcmc.py notices).  A mutant changes arithmetic, or an index clamped into the same array; never a size, a launch,
+// a barrier or a loop.  0 = the product;
+//   1 = srcf is kept in double: no Float32 rounding of the source's light
+//   2 = iota indexed by column, clamped to its H entries (img.iota[min(P.off_w + w2, img.H - 1)])
+//   3 = a NaN pixel still subtracts its rate
+//   4 = lgs is not subtracted
+//   5 = ang is accepted up to 2 * M_PI
+//   6 = llscale uses log(s) for log(sc * s)
+// Never defined in the shipped build.
+#ifndef CELESTE_MCMC_MUTANT
+#define CELESTE_MCMC_MUTANT 0
+#endif
+
 #define MC_D CELESTE_MCMC_D
 #define MC_STEP_OUT 10        // max_steps_out (slicesample.jl:24)
 #define MC_ACCEPT_MAX 1000    // acceptable's loop guard (slicesample.jl:58-62)
@@ -195,16 +209,32 @@ __device__ double mc_loglike(const McArgs &A, int ti, int model, const double *t
             const int w2 = idx / P.H2, h2 = idx - w2 * P.H2;
             const double hh = (double)(P.off_h + h2 + 1), ww = (double)(P.off_w + w2 + 1);
             const double f = model == 0 ? star_value(coef, hh + sh0, ww + sw0) : galaxy_value(tc, A.NC, hh - m1, ww - m2, etab);
+#if CELESTE_MCMC_MUTANT == 1
+            const double srcf = f * flux;
+#else
             const float srcf = (float)(f * flux);                                           // src_pixels::Float32
+#endif
+#if CELESTE_MCMC_MUTANT == 2
+            const double rate = ((double)srcf + A.bg[po + idx]) * (double)img.iota[min(P.off_w + w2, img.H - 1)];
+#else
             const double rate = ((double)srcf + A.bg[po + idx]) * (double)img.iota[P.off_h + h2];
+#endif
             inf |= isinf(rate);
             const double x = A.data[po + idx];
+#if CELESTE_MCMC_MUTANT == 3
+            acc += isnan(x) ? -rate : x * log(rate) - rate;
+#else
             if (!isnan(x)) acc += x * log(rate) - rate;
+#endif
         }
         lgs += A.lg[v];
     }
     if (__any(inf)) return -INFINITY;
+#if CELESTE_MCMC_MUTANT == 4
+    return wave_sum(acc);
+#else
     return wave_sum(acc) - lgs;
+#endif
 }
 
 __device__ inline double mc_logsumexp8(const double *x) {
@@ -248,12 +278,20 @@ __device__ double mc_logprior(const McPrior &pr, int model, const double *th, co
     // make_gal_logprior (:372-411)
     const double dev = th[7], ab = th[8], ang = th[9], sc = th[10];
     double g;
+#if CELESTE_MCMC_MUTANT == 5
+    if (!mc_inrange(dev, 0.0, 1.0) || !mc_inrange(ab, 0.0, 1.0) || !mc_inrange(ang, 0.0, 2 * M_PI) || !mc_inrange(sc, 1e-5, INFINITY))
+#else
     if (!mc_inrange(dev, 0.0, 1.0) || !mc_inrange(ab, 0.0, 1.0) || !mc_inrange(ang, 0.0, M_PI) || !mc_inrange(sc, 1e-5, INFINITY))
+#endif
         g = -INFINITY;
     else {
         const double mu = pr.pd.p.gal_radius_px_mean, s = sqrt(pr.pd.p.gal_radius_px_var);
         const double z = (log(sc) - mu) / s;
+#if CELESTE_MCMC_MUTANT == 6
+        const double llscale = -0.5 * z * z - log(s) - 0.5 * log(2.0 * M_PI);
+#else
         const double llscale = -0.5 * z * z - log(sc * s) - 0.5 * log(2.0 * M_PI);     // LogNormal(mean, sqrt(var))
+#endif
         g = mc_logflux_prior(pr, 1, th) + (-log(M_PI)) + llscale;
     }
     return g + pos;

@@ -22,6 +22,20 @@
 #include "../engine_client.h"
 #include "../../../include/celeste_phot.h"
 
+// Mutation testing (tests/test_satellite_mutants.py builds this library with -DCELESTE_PHOT_MUTANT=k and checks that
+// tests/test_gpu_phot.py notices).  A mutant changes arithmetic, or an index that stays under the same p < npx test; never a
+// size, a launch, a barrier or a loop.  0 = the product;
+//   1 = phot_pass reads pixel t * 64 + lane: t0 is dropped (t < nt <= n_tiles, and p < npx is still tested)
+//   2 = b leaves out the neighbours' light
+//   3 = elec tests px[p] >= 0.0: AT_BOUND is never reached
+//   4 = the summary weights are 1 / sigma instead of 1 / sigma^2
+//   5 = the convergence test compares fabs(step) with tol_sigma itself
+//   6 = the second pass's sigma is 1 / s0 without the square root
+// Never defined in the shipped build.
+#ifndef CELESTE_PHOT_MUTANT
+#define CELESTE_PHOT_MUTANT 0
+#endif
+
 #define PHOT_NB CELESTE_PHOT_BANDS
 #define PHOT_NSUM CELESTE_PHOT_NSUMMARY
 #define PHOT_THREADS 256
@@ -55,7 +69,11 @@ phot_pixel_kernel(const VisitItem *__restrict__ items, const DevImage *__restric
         const bool inp = px.inp, valid = px.valid;
         const float xf = px.xf, skyf = px.skyf;
         const double iota = px.iota, m = px.m, B = px.B;
+#if CELESTE_PHOT_MUTANT == 2
+        const double a = __dmul_rn(iota, m), b = __dmul_rn(iota, (double)skyf);
+#else
         const double a = __dmul_rn(iota, m), b = __dmul_rn(iota, (double)skyf + B);
+#endif
         const bool bad = valid && !(isfinite(a) && isfinite(b) && a >= 0.0 && b > 0.0);
         if (inp) {                                            // idx < npx: inside the entry's planes
             const int64_t o = it.px_off + idx;
@@ -85,7 +103,11 @@ __device__ __forceinline__ void phot_pass(const double *pa, const double *pb, co
         double (*buf)[3] = part[round & 1];
         const int nt = min(n_tiles - t0, PHOT_PT);
         for (int t = wave; t < nt; t += PHOT_WAVES) {
+#if CELESTE_PHOT_MUTANT == 1
+            const int p = t * 64 + lane;
+#else
             const int p = (t0 + t) * 64 + lane;
+#endif
             double a = 0.0, b = 0.0, x = 0.0;
             if (p < npx) { a = pa[p]; b = pb[p]; x = px[p]; }
             double u0 = 0.0, u1 = 0.0, u2 = 0.0;
@@ -168,7 +190,11 @@ phot_solve_kernel(const int32_t *__restrict__ list, const PhotEntry *__restrict_
             if (b > 0.0 && a > 0.0) {
                 light = 1;
                 amin = fmax(amin, -b / a);
+#if CELESTE_PHOT_MUTANT == 3
+                if (px[p] >= 0.0) elec = 1;
+#else
                 if (px[p] > 0.0) elec = 1;
+#endif
             }
         }
         amin = wave_max(amin);
@@ -197,10 +223,18 @@ phot_solve_kernel(const int32_t *__restrict__ list, const PhotEntry *__restrict_
                 const bool inside = next > amin;
                 if (!inside) next = __dadd_rn(alpha, __dmul_rn(0.5, __dsub_rn(amin, alpha)));
                 alpha = next;
+#if CELESTE_PHOT_MUTANT == 5
+                if (inside && fabs(step) <= tol_sigma) { flag = CELESTE_PHOT_OK; break; }
+#else
                 if (inside && fabs(step) <= tol_sigma / sqrt(s2)) { flag = CELESTE_PHOT_OK; break; }
+#endif
             }
             phot_pass<1>(pa, pb, px, npx, n_tiles, alpha, part, round, s0, s1, s2);
+#if CELESTE_PHOT_MUTANT == 6
+            sigma = 1.0 / s0;
+#else
             sigma = 1.0 / sqrt(s0);
+#endif
             chi2 = s1;
         }
     }
@@ -234,7 +268,11 @@ phot_summary_kernel(const int64_t *__restrict__ eoff, const int32_t *__restrict_
         double W = 0.0, SA = 0.0;
         for (int64_t e = e0; e < e1; ++e) {
             if (flag[e] != CELESTE_PHOT_OK || band[e] != lane) continue;
+#if CELESTE_PHOT_MUTANT == 4
+            const double sg = sigma[e], w = 1.0 / sg;
+#else
             const double sg = sigma[e], w = 1.0 / __dmul_rn(sg, sg);
+#endif
             ++n;
             W = __dadd_rn(W, w);
             SA = __dadd_rn(SA, __dmul_rn(w, alpha[e]));
@@ -246,7 +284,11 @@ phot_summary_kernel(const int64_t *__restrict__ eoff, const int32_t *__restrict_
             cv = 0.0;
             for (int64_t e = e0; e < e1; ++e) {
                 if (flag[e] != CELESTE_PHOT_OK || band[e] != lane) continue;
+#if CELESTE_PHOT_MUTANT == 4
+                const double sg = sigma[e], w = 1.0 / sg, d = __dsub_rn(alpha[e], wmean);
+#else
                 const double sg = sigma[e], w = 1.0 / __dmul_rn(sg, sg), d = __dsub_rn(alpha[e], wmean);
+#endif
                 cv = __dadd_rn(cv, __dmul_rn(w, __dmul_rn(d, d)));
             }
         }

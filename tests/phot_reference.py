@@ -96,6 +96,26 @@ def solve(e: Entry) -> Entry:
     return e
 
 
+def newton_iters(e: Entry, tol_sigma, max_iters=50):
+    """The header's iteration on a solved OK entry, in extended precision: alpha_0 = 1, alpha_{k+1} = alpha_k + g / D with
+    D = sum x a^2 / lam^2, half of the way to alpha_min where a step would reach it, stopping once a step that stayed inside
+    has |step| <= tol_sigma / sqrt(I(alpha_k)).  Returns (steps taken, the smallest |log(|step| / threshold)| over the steps
+    tested: how far the count is from depending on rounding)."""
+    a, b, x = e.a.astype(LD), e.b.astype(LD), e.x.astype(LD)
+    alpha, margin = LD(1), np.inf
+    for k in range(1, max_iters + 1):
+        lam = b + alpha * a
+        g, D, I = (a * (x / lam - 1)).sum(), (x * a * a / lam ** 2).sum(), (a * a / lam).sum()
+        step = g / D
+        inside = alpha + step > e.alpha_min
+        alpha = alpha + step if inside else alpha + LD(0.5) * (LD(e.alpha_min) - alpha)
+        thr = LD(tol_sigma) / np.sqrt(I)
+        margin = min(margin, abs(float(np.log(abs(step) / thr))))
+        if inside and abs(step) <= thr:
+            return k, margin
+    return max_iters, margin
+
+
 def band_summaries(entries):
     """(n_epochs [5] int, summary [5, 3]) over the OK entries of every band in image order"""
     n_epochs, summary = np.zeros(NB, dtype=np.int32), np.full((NB, 3), np.nan)

@@ -141,6 +141,45 @@ def test_edge_scene_against_the_restatement(lib):
         assert (got.purity()[s] < 1).all()
 
 
+def test_explicit_bitmaps_against_the_restatement(lib):
+    """Patches whose bitmaps leave pixels unset that are not NaN, so that the library gets them as explicit bitmaps (a bitmap
+    equal to the NaN mask is not passed at all, and no other test here has another).  Source 0: a 9 x 13 patch, an ellipse with
+    one more pixel unset; source 1: a 9 x 9 patch that overlaps it, a disc.  Rows 18 .. 24, columns 23 .. 26 (1-based) are
+    shared; of these (18, 23), (18, 24), (18, 25), (19, 23) are set in 0's bitmap and unset in 1's, and (24, 26) the other way.
+    For CELESTE_CLIENT_MUTANT 3 (the neighbour's bitmap ignored: 1's light at those four pixels of 0's stamps) and 4 (the
+    target's bitmap read transposed: wrong on a patch that is not square)."""
+    from celeste_jl_amd import synthetic
+    from celeste_jl_amd.model import ImagePatch, neighbor_map
+    from celeste_jl_amd.params import catalog_init_source
+    images = synthetic.blank_images(48, 60)
+    catalog = [synthetic.sample_ce([20.2, 20.3], False), synthetic.sample_ce([22.3, 27.2], True)]
+    synthetic.gen_images(images, catalog, np.random.Generator(np.random.PCG64(13)))
+    boxes = [((16, 24), (14, 26)), ((18, 26), (23, 31))]
+    hh, ww = np.arange(1, 49)[:, None], np.arange(1, 61)[None, :]
+    masks = [((hh - 20) / 4.6) ** 2 + ((ww - 20) / 6.6) ** 2 <= 1.0, (hh - 22) ** 2 + (ww - 27) ** 2 <= 4.3 ** 2]
+    masks[0][17, 16] = False                                      # (18, 17): off both axes of the ellipse
+    patches = [[ImagePatch.from_box(img, box) for img in images] for box in boxes]
+    for row, box, mask in zip(patches, boxes, masks):
+        for p in row:
+            p.active_pixel_bitmap = p.active_pixel_bitmap & mask[box[0][0] - 1:box[0][1], box[1][0] - 1:box[1][1]]
+    assert [p.active_pixel_bitmap.shape for p in (patches[0][0], patches[1][0])] == [(9, 13), (9, 9)]
+    assert not np.isnan(images[0].pixels).any() and not patches[0][0].active_pixel_bitmap.all() and not patches[1][0].active_pixel_bitmap.all()
+    for h, w in ((18, 23), (18, 24), (18, 25), (19, 23)):
+        assert masks[0][h - 1, w - 1] and not masks[1][h - 1, w - 1]
+    assert masks[1][23, 25] and not masks[0][23, 25]
+    assert not np.array_equal(patches[0][0].active_pixel_bitmap[:, :9], patches[0][0].active_pixel_bitmap[:, :9].T)
+    f = synthetic.Field(images, catalog, patches, neighbor_map(patches), np.stack([catalog_init_source(ce) for ce in catalog]),
+                        "bitmaps")
+    assert f.neighbors == [[1], [0]]
+    ref = FR.fit_reference(f.images, f.patches, f.neighbors, f.vp, [0, 1])
+    got = _run(f)
+    _compare(got, ref, "explicit bitmaps")
+    assert got.n_pix[0, 0] == int(patches[0][0].active_pixel_bitmap.sum()) < 9 * 13 and (got.status == 0).all()
+    # 1's light at a shared pixel it does not cover would be seen: it is far above the stamps' tolerance there
+    n, visited, E, m, B = FR.expected_nmgy(f.images, f.patches, f.neighbors, f.vp, 0)[2]
+    assert visited[2, 9] and B[2, 9] == 0 and B[3, 10] > 1e-6 * E[3, 10]     # (18, 23) unset in 1's disc; (19, 24) set
+
+
 def test_determinism_and_batch_invariance(lib):
     """the same bits for every target: the call made twice, the targets reversed, one target repeated, one call per target,
     another CELESTE_CHUNK_PX on a fresh context"""

@@ -57,6 +57,47 @@ def test_loglike_and_logprior_match_the_restatement(variable, nan_fraction, spar
         ctx.close()
 
 
+def test_logprior_at_the_edges_of_its_support_matches_the_restatement():
+    """mcmc_loglike at points on and just outside every bound of the prior's support, one coordinate moved at a time from an
+    interior point, for both models and two targets: the log prior is -inf exactly where the restatement's is, and within
+    1e-11 of it elsewhere.  (The random points of the test above stay well inside every bound, so a wider interval -- the angle
+    accepted up to 2 pi, CELESTE_MCMC_MUTANT 5 -- passed it.)  The likelihood at these points is not compared: the sampler
+    never evaluates it where the prior is -inf."""
+    f = synthetic.make_sample_dataset("two_body", seed=1)
+    prior = synthetic.load_prior()
+    targets = [0, 1]
+    base = np.array([1.4, 1.6, 1.5, 1.7, 1.3, 0.4, 0.6, 0.3, 0.6, 1.2, 2.0])
+    edges = {0: [(5, 0.0), (5, 1.0), (6, 0.0), (6, 1.0)]}
+    edges[1] = edges[0] + [(9, 0.0), (9, math.pi), (9, np.nextafter(math.pi, 0.0)), (9, 3.5),
+                           (8, 0.0), (8, 1.0), (7, 0.0), (7, 1.0), (10, 1e-5), (10, np.nextafter(1e-5, 1.0))]
+    ctx = FieldContext(f.images, f.patches, f.neighbors)
+    try:
+        boxes = mcmc.target_boxes(f.images, f.catalog, targets)
+        for model in (0, 1):
+            dim = 7 if model == 0 else 11
+            pts = [(None, None)] + edges[model]
+            th = np.tile(base, (len(pts) * len(targets), 1))
+            which = np.repeat(np.arange(len(targets)), len(pts))
+            for k, (d, v) in enumerate(pts * len(targets)):
+                if d is not None:
+                    th[k, d] = v
+            if model == 0:
+                th[:, 7:] = 0.0
+            _, lp = ctx.mcmc_loglike(f.catalog, targets, model, which, th[:, :dim], boxes=boxes)
+            n_inf = 0
+            for k, ti in enumerate(which):
+                want = ref.logprior(prior, model, th[k], boxes[ti])
+                if math.isinf(want):
+                    assert want < 0 and lp[k] == want, (model, k, pts[k % len(pts)], lp[k])
+                    n_inf += 1
+                else:
+                    assert math.isfinite(lp[k]) and lp[k] == pytest.approx(want, rel=1e-11), (model, k, pts[k % len(pts)], lp[k], want)
+            # inside: the interior point and, for the galaxy, the two points just inside a bound
+            assert n_inf == len(targets) * (len(pts) - (1 if model == 0 else 3)), (model, n_inf)
+    finally:
+        ctx.close()
+
+
 def test_no_nan_at_prior_draws_with_a_zero_background():
     """test_mcmc.jl: 25-pixel patches, no sky, no neighbours -- the likelihood at prior draws is never NaN"""
     f = synthetic.make_sample_dataset("star", seed=2)

@@ -213,6 +213,60 @@ def test_a_patch_above_the_capacity_of_lds(lib):
     assert _same(_run(f, lds_max_pixels=64), got)
 
 
+def _boxed_field(H, W, boxes, seed, name):
+    """one source at the centre of each 1-based inclusive box ((h_lo, h_hi), (w_lo, w_hi)), galaxies and stars in turn, on
+    blank_images(H, W); returns (Field, restatement)"""
+    from celeste_jl_amd import synthetic
+    from celeste_jl_amd.model import ImagePatch, neighbor_map
+    from celeste_jl_amd.params import catalog_init_source
+    images = synthetic.blank_images(H, W)
+    catalog = [synthetic.sample_ce([(h[0] + h[1]) / 2 + 0.2, (w[0] + w[1]) / 2 - 0.3], k % 2 == 1) for k, (h, w) in enumerate(boxes)]
+    synthetic.gen_images(images, catalog, np.random.Generator(np.random.PCG64(seed)))
+    patches = [[ImagePatch.from_box(img, box) for img in images] for box in boxes]
+    f = synthetic.Field(images, catalog, patches, neighbor_map(patches), np.stack([catalog_init_source(ce) for ce in catalog]), name)
+    return f, PR.phot_reference(f.images, f.patches, f.neighbors, f.vp, list(range(len(catalog))))
+
+
+def test_two_rounds_of_tiles_against_the_restatement(lib):
+    """one 91 x 91 patch (8281 pixels, 130 tiles) per image: phot_pass takes tiles in rounds of 128, so the second round
+    (t0 = 128: pixels 8192 .. 8280, the other LDS buffer, the sums carried across rounds) runs in every pass.  For
+    CELESTE_PHOT_MUTANT 1 (t0 dropped), which no patch of at most 128 tiles can see."""
+    f, ref = _boxed_field(100, 100, [((5, 95), (5, 95))], 91, "91 x 91")
+    assert f.patches[0][0].active_pixel_bitmap.shape == (91, 91) and (91 * 91 + 63) // 64 == 130
+    got = _run(f)
+    _compare(got, ref, "91 x 91")
+    assert (got.flag == 0).all() and (got.n_pix == 8281).all() and len(got.n_pix) == 5
+    assert _same(_run(f, lds_max_pixels=64), got)
+
+
+# the LDS path's size classes end at 704, 1664 and 3072 pixels: a patch on each end, one just above it, and two small ones
+CLASS_BOXES = [((1, 53), (1, 58)),        # 0: 53 x 58 = 3074, the first size of the last class
+               ((53, 100), (1, 64)),      # 1: 48 x 64 = 3072; shares row 53 with 0
+               ((1, 26), (37, 100)),      # 2: 26 x 64 = 1664; shares columns 37 .. 58 with 0
+               ((27, 63), (56, 100)),     # 3: 37 x 45 = 1665; overlaps 0 and 1
+               ((64, 85), (65, 96)),      # 4: 22 x 32 = 704
+               ((86, 100), (54, 100)),    # 5: 15 x 47 = 705; overlaps 1
+               ((30, 38), (20, 28)),      # 6: 9 x 9, inside 0's patch
+               ((70, 86), (20, 36))]      # 7: 17 x 17, inside 1's
+CLASS_PIXELS = [3074, 3072, 1664, 1665, 704, 705, 81, 289]
+
+
+def test_size_classes_of_the_lds_path_against_the_restatement(lib):
+    """One call whose entries fall into every size class of the LDS path, on both sides of every class end, so that every class
+    launch but the last holds patches smaller than the one its dynamic LDS was sized for (the staging's `pad` is then the
+    entry's own, not the launch's); lds_max_pixels of 64, 704 and 1664 moves the class ends and streams what lies above."""
+    from celeste_jl_amd import phot
+    f, ref = _boxed_field(100, 100, CLASS_BOXES, 17, "size classes")
+    assert [[p.active_pixel_bitmap.size for p in row] for row in f.patches] == [[n] * 5 for n in CLASS_PIXELS]
+    assert 3074 <= phot.LDS_PIXELS and 0 in f.neighbors[6] and {0, 3, 5, 7} <= set(f.neighbors[1]) and f.neighbors[4] == []
+    got = _run(f)
+    _compare(got, ref, "size classes")
+    assert got.n_pix.tolist() == [n for n in CLASS_PIXELS for _ in range(5)] and (got.status == 0).all()
+    assert (got.flag == 0).all()
+    for cap in (64, 704, 1664):
+        assert _same(_run(f, lds_max_pixels=cap), got), cap
+
+
 def test_determinism_and_batch_invariance(lib):
     """the same bits for every entry: the call made twice, the targets reversed, one target repeated, one call per target,
     another CELESTE_CHUNK_PX on a fresh context"""
@@ -255,6 +309,28 @@ def test_max_iters_and_tolerance(lib):
     loose = _run(f, tol_sigma=1e-3)
     assert (loose.iters <= a.iters).all() and (loose.iters[solved] < a.iters[solved]).any() and (loose.flag == a.flag).all()
     assert (np.abs(loose.alpha - a.alpha)[solved] <= 1e-3 * a.sigma[solved]).all()
+
+
+def test_newton_step_counts_against_the_restatement(lib):
+    """iters is the number of Newton steps the header's rule takes: |step| <= tol_sigma / sqrt(I(alpha_k)), restated in extended
+    precision (phot_reference.newton_iters).  On this scene sigma is below 1e-2, so a threshold that is not scaled by sigma is
+    at least 100 times looser and stops a step earlier; alpha is then still within ROOT_TOL of the root (Newton converges
+    quadratically), which is why the parity of alpha alone did not see CELESTE_PHOT_MUTANT 5.  An entry with a step within
+    0.1 % of its threshold is left out: there the count may depend on rounding."""
+    f, ref = _edge_scene()
+    ok = [i for i, e in enumerate(ref.flat) if e.flag == PR.OK]
+    assert len(ok) >= 30 and all(ref.flat[i].sigma < 1e-2 for i in ok)
+    for tol in (1e-3, 1e-6):
+        got = _run(f, tol_sigma=tol)
+        n = 0
+        for i in ok:
+            want, margin = PR.newton_iters(ref.flat[i], tol)
+            if margin < 1e-3:
+                continue
+            n += 1
+            assert got.flag[i] == PR.OK and got.iters[i] == want, (tol, i, got.iters[i], want, margin)
+        print("Newton step counts at tol_sigma %.0e: %d entries compared, %d to %d steps" % (tol, n, got.iters[ok].min(), got.iters[ok].max()))
+        assert n >= 30, (tol, n)
 
 
 def test_a_non_finite_row_fails_its_target_alone(lib):
