@@ -100,9 +100,50 @@ def light_curve_columns(lc) -> Dict[str, Optional[float]]:
     return {"n_epochs_r": n, "var_chi2_r": v if math.isfinite(v) else None}
 
 
-def celeste_to_rows(results, diagnostics: bool = False, light_curves: bool = False) -> List[Dict[str, Optional[float]]]:
+UNCERTAINTY_COLUMNS = ("ra_stderr", "dec_stderr", "ra_dec_corr", "gal_frac_dev_stderr", "gal_axis_ratio_stderr",
+                       "gal_angle_deg_stderr", "gal_radius_px_stderr")
+
+
+def uncertainty_columns(ub, vs) -> Dict[str, Optional[float]]:
+    """the Cramer-Rao columns of one result (info.InfoBounds of infer_box(..., uncertainties=True)) whose row is vs.  The
+    positions come from the block of the row's type (is_star > 0.5: the star's), in the units of pos, without a cos(dec)
+    factor; the four shape columns are the galaxy block's and None for a star row.  gal_radius_px_stderr is the delta-method
+    error of the column's own quantity radius * sqrt(axis_ratio), from the (axis_ratio, radius) sub-block; gal_angle_deg_stderr
+    is in degrees.  None where the result carries no `uncertainty`, where the value is not finite, or where the block is
+    flagged NO_PIXELS or NOT_POSITIVE."""
+    out: Dict[str, Optional[float]] = {name: None for name in UNCERTAINTY_COLUMNS}
+    if ub is None:
+        return out
+    from . import info
+    vs = np.asarray(vs, dtype=np.float64)
+    t = int(ub.chosen(vs))
+    if int(ub.flag[t]) & (info.NO_PIXELS | info.NOT_POSITIVE):
+        return out
+
+    def num(x):
+        x = float(x)
+        return x if math.isfinite(x) else None
+    c = ub.cov(t)
+    with np.errstate(invalid="ignore"):
+        out["ra_stderr"], out["dec_stderr"] = num(np.sqrt(c[0, 0])), num(np.sqrt(c[1, 1]))
+        out["ra_dec_corr"] = num(ub.pos_corr(t))
+        if t == info.GALAXY:
+            se = ub.shape_stderr()
+            out["gal_frac_dev_stderr"], out["gal_axis_ratio_stderr"] = num(se[0]), num(se[1])
+            out["gal_angle_deg_stderr"] = num(180 / math.pi * se[2])
+            # d(radius sqrt(q)) / d(q, radius) = (radius / (2 sqrt(q)), sqrt(q))
+            q, r = float(vs[ids.gal_axis_ratio]), float(vs[ids.gal_radius_px])
+            if q > 0:
+                gq, gr = r / (2 * math.sqrt(q)), math.sqrt(q)
+                a, b = info.AXIS_RATIO, info.RADIUS
+                out["gal_radius_px_stderr"] = num(np.sqrt(gq * gq * c[a, a] + 2 * gq * gr * c[a, b] + gr * gr * c[b, b]))
+    return out
+
+
+def celeste_to_rows(results, diagnostics: bool = False, light_curves: bool = False,
+                    uncertainties: bool = False) -> List[Dict[str, Optional[float]]]:
     """one row per OptimizedSource whose sky is not flagged bad; diagnostics: each row also gets DIAGNOSTIC_COLUMNS;
-    light_curves: each row also gets LIGHT_CURVE_COLUMNS"""
+    light_curves: each row also gets LIGHT_CURVE_COLUMNS; uncertainties: each row also gets UNCERTAINTY_COLUMNS"""
     rows = [variational_parameters_to_row(r.vs) for r in results if not r.is_sky_bad]
     if diagnostics:
         for row, r in zip(rows, [r for r in results if not r.is_sky_bad]):
@@ -110,6 +151,9 @@ def celeste_to_rows(results, diagnostics: bool = False, light_curves: bool = Fal
     if light_curves:
         for row, r in zip(rows, [r for r in results if not r.is_sky_bad]):
             row.update(light_curve_columns(getattr(r, "light_curve", None)))
+    if uncertainties:
+        for row, r in zip(rows, [r for r in results if not r.is_sky_bad]):
+            row.update(uncertainty_columns(getattr(r, "uncertainty", None), r.vs))
     return rows
 
 

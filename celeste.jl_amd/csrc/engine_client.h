@@ -1,13 +1,14 @@
-// engine_client.h -- what the libraries that compile the engine into themselves (blend, fit, phot) share.
+// engine_client.h -- what the libraries that compile the engine into themselves (blend, fit, phot, info) share.
 //
 // Included right after celeste_abi.hip, whose celeste_ctx, HIP_TRY, Comp, SrcImg, DevPatch, table_entry ... it uses; the engine
 // does not include it.  Everything here is static or __device__ __forceinline__: no library's export map knows of it.
 //   host    a context base (engine context, growable device buffers, stage events, stage times) with its create and destroy,
-//           the status fold; for the libraries that walk pixel visits (fit, phot): the target check, the prep_kernel launch at
-//           the call's table, the stage times, the work item and the walk over (target, non-empty visit, chunk)
+//           the status fold; for the libraries that walk pixel visits (fit, phot, info): the target check, the prep_kernel
+//           launch at the call's table, the stage times, the work item and the walk over (target, non-empty visit, chunk)
 //   device  one source's light at a pixel, the staging of its components, the wavefront maximum, the non-finite test of a
 //           parameter row, and the pixel walk of a work item with the ELBO's neighbour rule (visit_pixel_walk)
 #pragma once
+#include <type_traits>
 
 // Mutation testing (tests/test_satellite_mutants.py builds fit and phot with -DCELESTE_CLIENT_MUTANT=k and checks that their
 // parity tests notice; its own macro, because both libraries compile the engine, whose CELESTE_MUTANT numbers keep their
@@ -97,7 +98,7 @@ static inline int client_first_status(const int32_t *status, int32_t n) {
     return CELESTE_OK;
 }
 
-// ---- host: a call over pixel visits (fit, phot) ----------------------------------------------------------------------------
+// ---- host: a call over pixel visits (fit, phot, info) ----------------------------------------------------------------------
 static inline bool client_targets_ok(const celeste_ctx_t *c, int32_t n_targets, const int32_t *targets) {
     for (int ti = 0; ti < n_targets; ++ti)
         if (targets[ti] < 0 || targets[ti] >= c->S) return false;
@@ -194,11 +195,24 @@ struct VisitPixel {
     double B;                          // the neighbours' light
 };
 
+// What a tile_fn that takes a third argument gets besides (info: the densities' gradients are its own work): the target's
+// staged components and the exponential's table (LDS), its spline coefficients, its pixel-space position, the lane's 1-based
+// image coordinates, and whether the target's own light counts at the pixel (visited and not in the patch's last column)
+struct VisitOwn {
+    const Comp *tc;
+    const double *etab;
+    const double *coef;
+    double m1, m2;
+    double hh, ww;
+    bool own;
+};
+
 // The pixel walk of a work item by its wavefront (a workgroup of 64): for each 64-pixel tile of the chunk a lane owns a pixel and
-// calls tile_fn(img, px) -- in uniform control flow, so tile_fn may use wavefront operations.  The neighbour rule: B adds each
-// neighbour listed for the target that has an entry for the image, whose patch holds the pixel strictly inside (not in its
-// last column, :349) and whose bitmap has it set, evaluated at the pixel -- per link, not once per neighbour pixel.  A
-// neighbour no lane of the tile needs is skipped without staging its components.
+// calls tile_fn(img, px) -- or tile_fn(img, px, own) where tile_fn takes a VisitOwn -- in uniform control flow, so tile_fn may
+// use wavefront operations.  The neighbour rule: B adds each neighbour listed for the target that has an entry for the image,
+// whose patch holds the pixel strictly inside (not in its last column, :349) and whose bitmap has it set, evaluated at the
+// pixel -- per link, not once per neighbour pixel.  A neighbour no lane of the tile needs is skipped without staging its
+// components.
 // The tables are the kernel's own __restrict__ parameters, passed on one by one: a struct of them loses the no-alias
 // information and with it the scalar loads.  The pixel goes to tile_fn as one struct by reference and tile_fn reads it into
 // locals first; with ten arguments by value the compiler folds phot's soundness test another way (two more VGPRs).
@@ -251,10 +265,11 @@ __device__ __forceinline__ void visit_pixel_walk(const VisitItem &it, const DevI
         const double hh = (double)(h0 + 1), ww = (double)(w0 + 1);
         double m = 0.0;
 #if CELESTE_CLIENT_MUTANT == 1
-        if (valid && w2 < W2) m = visit_light(si, tc, NC, coef, etab, hh, ww);
+        const bool own = valid && w2 < W2;
 #else
-        if (valid && w2 < W2 - 1) m = visit_light(si, tc, NC, coef, etab, hh, ww);
+        const bool own = valid && w2 < W2 - 1;
 #endif
+        if (own) m = visit_light(si, tc, NC, coef, etab, hh, ww);
         double B = 0.0;
         for (int64_t q = nb0; q < nb1; ++q) {
             const int v2 = table_entry(vis_off, vis_img, dense, N, nbr_idx[q], n);
@@ -282,6 +297,11 @@ __device__ __forceinline__ void visit_pixel_walk(const VisitItem &it, const DevI
 #endif
         }
         const VisitPixel px = {tile, idx, inp, valid, xf, skyf, iota, m, B};
-        tile_fn(img, px);
+        if constexpr (std::is_invocable_v<F, const DevImage &, const VisitPixel &, const VisitOwn &>) {
+            const VisitOwn ow = {tc, etab, coef, si.m1, si.m2, hh, ww, own};
+            tile_fn(img, px, ow);
+        } else {
+            tile_fn(img, px);
+        }
     }
 }

@@ -187,6 +187,7 @@ class OptimizedSource:
     failed: bool = False   # the optimiser reported a non-finite ELBO for this source; vs is its last good row
     fit: Optional[object] = None   # infer_box(..., diagnostics=True): this source's fit.FitStats at the final parameters
     light_curve: Optional[object] = None   # infer_box(..., light_curves=True): this source's phot.LightCurves (one target)
+    uncertainty: Optional[object] = None   # infer_box(..., uncertainties=True): this source's info.InfoBounds (one target)
 
 
 def bad_sky(ce, images) -> bool:
@@ -303,7 +304,8 @@ def group_joint_infer(group, catalog, target_sources: Sequence[int], neighbors: 
 def infer_box(images, box: BoundingBox, catalog=None, method: str = "joint_vi", cfg: Optional[ElboConfig] = None,
               n_iters: int = NUM_JOINT_VI_ITERS, device: int = 0, schedule: str = "cyclades",
               devices: Optional[Sequence[int]] = None, match_radius: float = 1.0 / 3600.0,
-              mcmc_config=None, prep: str = "host", diagnostics: bool = False, light_curves: bool = False) -> list:
+              mcmc_config=None, prep: str = "host", diagnostics: bool = False, light_curves: bool = False,
+              uncertainties: bool = False) -> list:
     """infer_box / _infer_box (ParallelRun.jl:610-672): targets = catalog entries strictly inside the box, neighbours
     may lie outside it, then joint or single variational inference on the device (method in {joint_vi, single_vi}:
     one OptimizedSource per target) or MCMC (method = "mcmc": process_source_mcmc, ParallelRun.jl:504-543, with
@@ -325,21 +327,27 @@ def infer_box(images, box: BoundingBox, catalog=None, method: str = "joint_vi", 
     light_curves: after variational inference every result also carries `light_curve`, the per-exposure forced photometry of
     its source (phot.LightCurves of one target: per image the scale of its light, its error, a flag; per band the weighted mean
     and the variability chi-square; include/celeste_phot.h) at the same table.  Not available with method="mcmc".  The default
-    loads nothing and changes nothing."""
+    loads nothing and changes nothing.
+    uncertainties: after variational inference every result also carries `uncertainty`, the Cramer-Rao bounds of its source's
+    position and shape from the pixels' Fisher information (info.InfoBounds of one target: per type the sums, the covariance
+    and its flags; include/celeste_info.h) at the same table.  Not available with method="mcmc".  The default loads nothing
+    and changes nothing."""
     if prep not in ("host", "device"):
         raise ValueError("prep must be 'host' or 'device', not %r" % (prep,))
     if diagnostics and method == "mcmc":
         raise ValueError("diagnostics=True needs a parameter table: method='mcmc' returns samples, not parameters")
     if light_curves and method == "mcmc":
         raise ValueError("light_curves=True needs a parameter table: method='mcmc' returns samples, not parameters")
+    if uncertainties and method == "mcmc":
+        raise ValueError("uncertainties=True needs a parameter table: method='mcmc' returns samples, not parameters")
     if method == "mcmc" and devices is not None:
         raise ValueError("method='mcmc' runs on one device: pass device=..., not devices=... (device groups run VI only)")
     if catalog is None:
         if prep == "device":
             return _infer_box_detected_table(images, box, method, cfg, n_iters, device, schedule, devices, match_radius, mcmc_config,
-                                             diagnostics, light_curves)
+                                             diagnostics, light_curves, uncertainties)
         return _infer_box_detected(images, box, method, cfg, n_iters, device, schedule, devices, match_radius, mcmc_config,
-                                   diagnostics, light_curves)
+                                   diagnostics, light_curves, uncertainties)
     targets = [i for i, ce in enumerate(catalog) if box.contains(ce.pos)]
     if not targets:
         return []
@@ -347,16 +355,18 @@ def infer_box(images, box: BoundingBox, catalog=None, method: str = "joint_vi", 
         from .prep import PrepImages
         with PrepImages(images, devices[0] if devices is not None else device) as pi:
             return _infer_box_catalog(images, catalog, targets, method, cfg, n_iters, device, schedule, devices, mcmc_config, pi,
-                                      diagnostics, light_curves)
+                                      diagnostics, light_curves, uncertainties)
     return _infer_box_catalog(images, catalog, targets, method, cfg, n_iters, device, schedule, devices, mcmc_config, None,
-                              diagnostics, light_curves)
+                              diagnostics, light_curves, uncertainties)
 
 
-def _with_fit(results: list, diagnostics: bool, problem, catalog, targets, device: int, light_curves: bool = False) -> list:
+def _with_fit(results: list, diagnostics: bool, problem, catalog, targets, device: int, light_curves: bool = False,
+              uncertainties: bool = False) -> list:
     """infer_box(..., diagnostics=True): every result gets the fit statistics of its source (fit.FitContext.stats) at the
     table that holds the targets' optimised rows and catalog_init_source for every other source; light_curves=True: its
-    per-exposure photometry (phot.PhotContext.light_curves) at the same table"""
-    if not (diagnostics or light_curves) or not results:
+    per-exposure photometry (phot.PhotContext.light_curves) at the same table; uncertainties=True: the bounds of its position
+    and shape (info.InfoContext.bounds) at the same table"""
+    if not (diagnostics or light_curves or uncertainties) or not results:
         return results
     vp = init_source_table(catalog)
     vp[list(targets)] = np.stack([r.vs for r in results])
@@ -372,11 +382,18 @@ def _with_fit(results: list, diagnostics: bool, problem, catalog, targets, devic
             lc = pc.light_curves(vp, list(targets))
         for k, r in enumerate(results):
             r.light_curve = lc[k]
+    if uncertainties:
+        from .info import InfoContext
+        with InfoContext(problem, device) as ic:
+            ub = ic.bounds(vp, list(targets))
+        for k, r in enumerate(results):
+            r.uncertainty = ub[k]
     return results
 
 
 def _infer_box_catalog(images, catalog, targets, method, cfg, n_iters, device, schedule, devices, mcmc_config, pi,
-                       diagnostics: bool = False, light_curves: bool = False) -> list:
+                       diagnostics: bool = False, light_curves: bool = False,
+                       uncertainties: bool = False) -> list:
     """infer_box with a catalog.  pi: a prep.PrepImages over `images` (the table, neighbour lists, stamps and sky flags come
     from the device) or None (from the host)."""
     def sky_flags(dev):
@@ -411,7 +428,8 @@ def _infer_box_catalog(images, catalog, targets, method, cfg, n_iters, device, s
             group.close()
         flags = sky_flags(devices[0])
         return _with_fit([OptimizedSource(float(catalog[t].pos[0]), float(catalog[t].pos[1]), vs[k].copy(), flags[k], t in failed)
-                          for k, t in enumerate(targets)], diagnostics, group.problem, catalog, targets, devices[0], light_curves)
+                          for k, t in enumerate(targets)], diagnostics, group.problem, catalog, targets, devices[0], light_curves,
+                          uncertainties)
     # patches and neighbour lists as arrays (model.patch_table: the geometry of get_sky_patches / find_neighbors
     # without a Python object per patch); several fields: sources see a few images each -> sparse patch list
     ctx = FieldContext.from_catalog(images, catalog, device=device, sparse=len(images) > 5, prep_images=pi)
@@ -429,11 +447,13 @@ def _infer_box_catalog(images, catalog, targets, method, cfg, n_iters, device, s
         ctx.close()
     flags = sky_flags(device)
     return _with_fit([OptimizedSource(float(catalog[t].pos[0]), float(catalog[t].pos[1]), vs[k].copy(), flags[k], t in failed)
-                      for k, t in enumerate(targets)], diagnostics, ctx.problem, catalog, targets, device, light_curves)
+                      for k, t in enumerate(targets)], diagnostics, ctx.problem, catalog, targets, device, light_curves,
+                      uncertainties)
 
 
 def _infer_box_detected(images, box: BoundingBox, method, cfg, n_iters, device, schedule, devices,
-                        match_radius, mcmc_config=None, diagnostics: bool = False, light_curves: bool = False) -> list:
+                        match_radius, mcmc_config=None, diagnostics: bool = False, light_curves: bool = False,
+                        uncertainties: bool = False) -> list:
     """_infer_box with the catalog and patches of detect_sources (ParallelRun.jl:661-665): targets strictly inside the
     box, neighbours from the detection patches, the context (or device group) over those patches."""
     from .detect import detect_sources
@@ -485,11 +505,13 @@ def _infer_box_detected(images, box: BoundingBox, method, cfg, n_iters, device, 
         flag_device = device
     flags = bad_sky_flags([catalog[t] for t in targets], images, flag_device)
     return _with_fit([OptimizedSource(float(catalog[t].pos[0]), float(catalog[t].pos[1]), vs[k].copy(), flags[k], t in failed)
-                      for k, t in enumerate(targets)], diagnostics, problem, catalog, targets, flag_device, light_curves)
+                      for k, t in enumerate(targets)], diagnostics, problem, catalog, targets, flag_device, light_curves,
+                      uncertainties)
 
 
 def _infer_box_detected_table(images, box: BoundingBox, method, cfg, n_iters, device, schedule, devices,
-                              match_radius, mcmc_config=None, diagnostics: bool = False, light_curves: bool = False) -> list:
+                              match_radius, mcmc_config=None, diagnostics: bool = False, light_curves: bool = False,
+                              uncertainties: bool = False) -> list:
     """_infer_box_detected with the join, the catalog, the patch table, the neighbour lists and the sky flags from the device
     (detect.detect_table, prep.bad_sky_flags over one prep.PrepImages); the problem is cabi.problem_from_table's."""
     from . import cabi, prep
@@ -536,4 +558,5 @@ def _infer_box_detected_table(images, box: BoundingBox, method, cfg, n_iters, de
                 ctx.close()
         flags = prep.bad_sky_flags([catalog[t] for t in targets], images, prep_images=pi)
     return _with_fit([OptimizedSource(float(catalog[t].pos[0]), float(catalog[t].pos[1]), vs[k].copy(), flags[k], t in failed)
-                      for k, t in enumerate(targets)], diagnostics, problem, catalog, targets, first, light_curves)
+                      for k, t in enumerate(targets)], diagnostics, problem, catalog, targets, first, light_curves,
+                      uncertainties)

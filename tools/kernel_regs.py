@@ -1,5 +1,7 @@
 """Registers / scratch / LDS of every kernel in the compiled library, and VALU / LDS / FP64 instruction counts of the
-pixel kernel's loops (static, from the ISA; no GPU needed).  usage: python tools/kernel_regs.py [name-filter]"""
+pixel kernel's loops (static, from the ISA; no GPU needed).  usage: python tools/kernel_regs.py [name-filter [source]]
+source: a .hip file under csrc/ of a library that compiles the engine into itself, e.g. info/celeste_info.hip (default:
+celeste_abi.hip)"""
 import os
 import re
 import subprocess
@@ -10,17 +12,17 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "celeste.jl_amd", "csrc")
 
 
-def asm(extra=()):
+def asm(extra=(), src="celeste_abi.hip"):
     with tempfile.TemporaryDirectory() as tmp:
         out = os.path.join(tmp, "k.s")
         subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-S", "--cuda-device-only",
-                               "-o", out, os.path.join(CSRC, "celeste_abi.hip")] + list(extra), stderr=subprocess.DEVNULL)
+                               "-o", out, os.path.join(CSRC, src)] + list(extra), stderr=subprocess.DEVNULL)
         return open(out).read()
 
 
 def main():
     flt = sys.argv[1] if len(sys.argv) > 1 else "pixel_kernel"
-    txt = asm()
+    txt = asm(src=sys.argv[2]) if len(sys.argv) > 2 else asm()
     for m in re.finditer(r"^\s*\.amdhsa_kernel (\S+)", txt, re.M):
         name = m.group(1)
         if flt not in name:
