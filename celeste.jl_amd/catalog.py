@@ -141,9 +141,10 @@ def uncertainty_columns(ub, vs) -> Dict[str, Optional[float]]:
 
 
 def celeste_to_rows(results, diagnostics: bool = False, light_curves: bool = False,
-                    uncertainties: bool = False) -> List[Dict[str, Optional[float]]]:
+                    uncertainties: bool = False, refined: bool = False) -> List[Dict[str, Optional[float]]]:
     """one row per OptimizedSource whose sky is not flagged bad; diagnostics: each row also gets DIAGNOSTIC_COLUMNS;
-    light_curves: each row also gets LIGHT_CURVE_COLUMNS; uncertainties: each row also gets UNCERTAINTY_COLUMNS"""
+    light_curves: each row also gets LIGHT_CURVE_COLUMNS; uncertainties: each row also gets UNCERTAINTY_COLUMNS; refined: each
+    row also gets refine_round (infer_box(..., refine=k): the round of the residual search that added the source, else None)"""
     rows = [variational_parameters_to_row(r.vs) for r in results if not r.is_sky_bad]
     if diagnostics:
         for row, r in zip(rows, [r for r in results if not r.is_sky_bad]):
@@ -154,6 +155,9 @@ def celeste_to_rows(results, diagnostics: bool = False, light_curves: bool = Fal
     if uncertainties:
         for row, r in zip(rows, [r for r in results if not r.is_sky_bad]):
             row.update(uncertainty_columns(getattr(r, "uncertainty", None), r.vs))
+    if refined:
+        for row, r in zip(rows, [r for r in results if not r.is_sky_bad]):
+            row["refine_round"] = getattr(r, "refined", None)
     return rows
 
 

@@ -17,7 +17,7 @@ batch form one launch ("layer"): no two of them are neighbours, so optimising th
 the reference's schedule.
 """
 import logging
-from dataclasses import dataclass
+from dataclasses import dataclass, replace
 from typing import Callable, List, Optional, Sequence
 
 import numpy as np
@@ -188,6 +188,7 @@ class OptimizedSource:
     fit: Optional[object] = None   # infer_box(..., diagnostics=True): this source's fit.FitStats at the final parameters
     light_curve: Optional[object] = None   # infer_box(..., light_curves=True): this source's phot.LightCurves (one target)
     uncertainty: Optional[object] = None   # infer_box(..., uncertainties=True): this source's info.InfoBounds (one target)
+    refined: Optional[int] = None   # infer_box(..., refine=k): the round of the residual search that added this source; None: it was there from the start
 
 
 def bad_sky(ce, images) -> bool:
@@ -305,7 +306,7 @@ def infer_box(images, box: BoundingBox, catalog=None, method: str = "joint_vi", 
               n_iters: int = NUM_JOINT_VI_ITERS, device: int = 0, schedule: str = "cyclades",
               devices: Optional[Sequence[int]] = None, match_radius: float = 1.0 / 3600.0,
               mcmc_config=None, prep: str = "host", diagnostics: bool = False, light_curves: bool = False,
-              uncertainties: bool = False) -> list:
+              uncertainties: bool = False, refine: int = 0, refine_threshold: float = 5.0) -> list:
     """infer_box / _infer_box (ParallelRun.jl:610-672): targets = catalog entries strictly inside the box, neighbours
     may lie outside it, then joint or single variational inference on the device (method in {joint_vi, single_vi}:
     one OptimizedSource per target) or MCMC (method = "mcmc": process_source_mcmc, ParallelRun.jl:504-543, with
@@ -331,7 +332,63 @@ def infer_box(images, box: BoundingBox, catalog=None, method: str = "joint_vi", 
     uncertainties: after variational inference every result also carries `uncertainty`, the Cramer-Rao bounds of its source's
     position and shape from the pixels' Fisher information (info.InfoBounds of one target: per type the sums, the covariance
     and its flags; include/celeste_info.h) at the same table.  Not available with method="mcmc".  The default loads nothing
-    and changes nothing."""
+    and changes nothing.
+    refine: after variational inference, up to `refine` rounds of: search the frames' residuals at the final table for sources the
+    catalog missed (resid.ResidContext.search with threshold refine_threshold, resid.missed_sources; include/celeste_resid.h),
+    append those strictly inside the box to the catalog as stars, and run the catalog path again over the extended catalog with
+    targets = the old targets followed by the new ones; it stops early when a round adds nothing.  Every result carries
+    `refined`: the round that added its source, None for the others.  On the first device of a device group.  Not available
+    with method="mcmc".  The default loads nothing and changes nothing."""
+    if refine and method == "mcmc":
+        raise ValueError("refine needs a parameter table: method='mcmc' returns samples, not parameters")
+    if refine:
+        state: dict = {}
+        results = _infer_box_round(images, box, catalog, method, cfg, n_iters, device, schedule, devices, match_radius,
+                                   mcmc_config, prep, diagnostics, light_curves, uncertainties, state)
+        return _refine(images, box, results, state, int(refine), float(refine_threshold), method, cfg, n_iters, device, schedule,
+                       devices, mcmc_config, prep, diagnostics, light_curves, uncertainties)
+    return _infer_box_round(images, box, catalog, method, cfg, n_iters, device, schedule, devices, match_radius, mcmc_config,
+                            prep, diagnostics, light_curves, uncertainties, None)
+
+
+def _refine(images, box, results, state, rounds, threshold, method, cfg, n_iters, device, schedule, devices, mcmc_config, prep,
+            diagnostics, light_curves, uncertainties) -> list:
+    """infer_box(..., refine=rounds): the loop of residual search and renewed inference.  state: what the first inference left
+    (_with_fit: problem, catalog, targets, device); empty when the box held no target."""
+    if not results or not state:
+        return results
+    from . import resid
+    catalog, targets, problem, dev = list(state["catalog"]), list(state["targets"]), state["problem"], state["device"]
+    added = {}
+    for k in range(1, rounds + 1):
+        vp = init_source_table(catalog)
+        vp[targets] = np.stack([r.vs for r in results])
+        with resid.ResidContext(problem, dev) as rc:
+            _, entries = resid.missed_sources(rc.search(vp, threshold=threshold), images, catalog)
+        new = [ce for ce in entries if box.contains(ce.pos)]
+        if not new:
+            break
+        for i in range(len(new)):
+            added[len(catalog) + i] = k
+        targets = targets + list(range(len(catalog), len(catalog) + len(new)))
+        # (a detection's entry has flux 0 in a band without a detection, which the catalog path's patch radius refuses
+        # (imaged_sources.jl:205): such bands get the floor the new entries get; a given catalog has none)
+        catalog = [ce if (np.asarray(ce.star_fluxes) > 0).all() and (np.asarray(ce.gal_fluxes) > 0).all() else
+                   replace(ce, star_fluxes=np.maximum(ce.star_fluxes, resid.DEFAULT_FLUX_FLOOR_NMGY),
+                           gal_fluxes=np.maximum(ce.gal_fluxes, resid.DEFAULT_FLUX_FLOOR_NMGY)) for ce in catalog] + new
+        state = {}
+        results = _infer_box_round(images, box, catalog, method, cfg, n_iters, device, schedule, devices, 0.0, mcmc_config, prep,
+                                   diagnostics, light_curves, uncertainties, state, targets=targets)
+        problem = state["problem"]
+    for r, t in zip(results, targets):
+        r.refined = added.get(t)
+    return results
+
+
+def _infer_box_round(images, box, catalog, method, cfg, n_iters, device, schedule, devices, match_radius, mcmc_config, prep,
+                     diagnostics, light_curves, uncertainties, state, targets=None) -> list:
+    """one inference over a box (infer_box without its refinement).  state (a dict or None) receives what _with_fit saw;
+    targets: the target list of the catalog path when it is not "every entry inside the box" (a refinement round)"""
     if prep not in ("host", "device"):
         raise ValueError("prep must be 'host' or 'device', not %r" % (prep,))
     if diagnostics and method == "mcmc":
@@ -345,27 +402,31 @@ def infer_box(images, box: BoundingBox, catalog=None, method: str = "joint_vi", 
     if catalog is None:
         if prep == "device":
             return _infer_box_detected_table(images, box, method, cfg, n_iters, device, schedule, devices, match_radius, mcmc_config,
-                                             diagnostics, light_curves, uncertainties)
+                                             diagnostics, light_curves, uncertainties, state)
         return _infer_box_detected(images, box, method, cfg, n_iters, device, schedule, devices, match_radius, mcmc_config,
-                                   diagnostics, light_curves, uncertainties)
-    targets = [i for i, ce in enumerate(catalog) if box.contains(ce.pos)]
+                                   diagnostics, light_curves, uncertainties, state)
+    if targets is None:
+        targets = [i for i, ce in enumerate(catalog) if box.contains(ce.pos)]
     if not targets:
         return []
     if prep == "device":
         from .prep import PrepImages
         with PrepImages(images, devices[0] if devices is not None else device) as pi:
             return _infer_box_catalog(images, catalog, targets, method, cfg, n_iters, device, schedule, devices, mcmc_config, pi,
-                                      diagnostics, light_curves, uncertainties)
+                                      diagnostics, light_curves, uncertainties, state)
     return _infer_box_catalog(images, catalog, targets, method, cfg, n_iters, device, schedule, devices, mcmc_config, None,
-                              diagnostics, light_curves, uncertainties)
+                              diagnostics, light_curves, uncertainties, state)
 
 
 def _with_fit(results: list, diagnostics: bool, problem, catalog, targets, device: int, light_curves: bool = False,
-              uncertainties: bool = False) -> list:
+              uncertainties: bool = False, state: Optional[dict] = None) -> list:
     """infer_box(..., diagnostics=True): every result gets the fit statistics of its source (fit.FitContext.stats) at the
     table that holds the targets' optimised rows and catalog_init_source for every other source; light_curves=True: its
     per-exposure photometry (phot.PhotContext.light_curves) at the same table; uncertainties=True: the bounds of its position
-    and shape (info.InfoContext.bounds) at the same table"""
+    and shape (info.InfoContext.bounds) at the same table.  state (infer_box(..., refine=k)): receives the problem, the catalog,
+    the targets and the device"""
+    if state is not None:
+        state.update(problem=problem, catalog=catalog, targets=list(targets), device=device)
     if not (diagnostics or light_curves or uncertainties) or not results:
         return results
     vp = init_source_table(catalog)
@@ -393,7 +454,7 @@ def _with_fit(results: list, diagnostics: bool, problem, catalog, targets, devic
 
 def _infer_box_catalog(images, catalog, targets, method, cfg, n_iters, device, schedule, devices, mcmc_config, pi,
                        diagnostics: bool = False, light_curves: bool = False,
-                       uncertainties: bool = False) -> list:
+                       uncertainties: bool = False, state: Optional[dict] = None) -> list:
     """infer_box with a catalog.  pi: a prep.PrepImages over `images` (the table, neighbour lists, stamps and sky flags come
     from the device) or None (from the host)."""
     def sky_flags(dev):
@@ -429,7 +490,7 @@ def _infer_box_catalog(images, catalog, targets, method, cfg, n_iters, device, s
         flags = sky_flags(devices[0])
         return _with_fit([OptimizedSource(float(catalog[t].pos[0]), float(catalog[t].pos[1]), vs[k].copy(), flags[k], t in failed)
                           for k, t in enumerate(targets)], diagnostics, group.problem, catalog, targets, devices[0], light_curves,
-                          uncertainties)
+                          uncertainties, state)
     # patches and neighbour lists as arrays (model.patch_table: the geometry of get_sky_patches / find_neighbors
     # without a Python object per patch); several fields: sources see a few images each -> sparse patch list
     ctx = FieldContext.from_catalog(images, catalog, device=device, sparse=len(images) > 5, prep_images=pi)
@@ -448,12 +509,12 @@ def _infer_box_catalog(images, catalog, targets, method, cfg, n_iters, device, s
     flags = sky_flags(device)
     return _with_fit([OptimizedSource(float(catalog[t].pos[0]), float(catalog[t].pos[1]), vs[k].copy(), flags[k], t in failed)
                       for k, t in enumerate(targets)], diagnostics, ctx.problem, catalog, targets, device, light_curves,
-                      uncertainties)
+                      uncertainties, state)
 
 
 def _infer_box_detected(images, box: BoundingBox, method, cfg, n_iters, device, schedule, devices,
                         match_radius, mcmc_config=None, diagnostics: bool = False, light_curves: bool = False,
-                        uncertainties: bool = False) -> list:
+                        uncertainties: bool = False, state: Optional[dict] = None) -> list:
     """_infer_box with the catalog and patches of detect_sources (ParallelRun.jl:661-665): targets strictly inside the
     box, neighbours from the detection patches, the context (or device group) over those patches."""
     from .detect import detect_sources
@@ -506,12 +567,12 @@ def _infer_box_detected(images, box: BoundingBox, method, cfg, n_iters, device, 
     flags = bad_sky_flags([catalog[t] for t in targets], images, flag_device)
     return _with_fit([OptimizedSource(float(catalog[t].pos[0]), float(catalog[t].pos[1]), vs[k].copy(), flags[k], t in failed)
                       for k, t in enumerate(targets)], diagnostics, problem, catalog, targets, flag_device, light_curves,
-                      uncertainties)
+                      uncertainties, state)
 
 
 def _infer_box_detected_table(images, box: BoundingBox, method, cfg, n_iters, device, schedule, devices,
                               match_radius, mcmc_config=None, diagnostics: bool = False, light_curves: bool = False,
-                              uncertainties: bool = False) -> list:
+                              uncertainties: bool = False, state: Optional[dict] = None) -> list:
     """_infer_box_detected with the join, the catalog, the patch table, the neighbour lists and the sky flags from the device
     (detect.detect_table, prep.bad_sky_flags over one prep.PrepImages); the problem is cabi.problem_from_table's."""
     from . import cabi, prep
@@ -559,4 +620,4 @@ def _infer_box_detected_table(images, box: BoundingBox, method, cfg, n_iters, de
         flags = prep.bad_sky_flags([catalog[t] for t in targets], images, prep_images=pi)
     return _with_fit([OptimizedSource(float(catalog[t].pos[0]), float(catalog[t].pos[1]), vs[k].copy(), flags[k], t in failed)
                       for k, t in enumerate(targets)], diagnostics, problem, catalog, targets, first, light_curves,
-                      uncertainties)
+                      uncertainties, state)
