@@ -12,6 +12,7 @@
 //   resid_zrange_kernel    one workgroup per image: z_max, z_min
 //   peaks_count / peaks_scan / peaks_write   the peak rule per pixel, counts per 256 raster indices, an exclusive scan of
 //                          the counts by one workgroup, and the records in (image, raster index) order
+// The stack of a search's maps across images (celeste_resid_stack) is resid_stack.h: its kernels, its mutant switches.
 // No floating-point atomic anywhere; a pixel's numbers depend on its own image only.
 //
 // LDS of the filter: (32 + 24) x (16 + 24) doubles twice and 25 x 25 taps = 40.8 KB at the largest radius, so three
@@ -393,9 +394,14 @@ __global__ void resid_sample_kernel(int64_t n, const int32_t *__restrict__ image
     out[i] = N; out[n + i] = D; out[2 * n + i] = cov;
 }
 
+#include "resid_stack.h"
+
 // ---- host side ---------------------------------------------------------------------------------------------------------------
 enum { RB_VP = 0, RB_TILES, RB_TILE_VIS, RB_LAM, RB_N, RB_D, RB_Z, RB_COV, RB_REC, RB_FRAMES, RB_TAPS, RB_CIMG, RB_STARTS,
-       RB_PIMG, RB_COUNTS, RB_OFFSETS, RB_TOTAL, RB_CAND, RB_ZREC, RB_SLOT, RB_SAMPLE_IN, RB_SAMPLE_OUT, RB_COUNT };
+       RB_PIMG, RB_COUNTS, RB_OFFSETS, RB_TOTAL, RB_CAND, RB_ZREC, RB_SLOT, RB_SAMPLE_IN, RB_SAMPLE_OUT,
+       // the stack's
+       RB_SK_IMGS, RB_SK_WTS, RB_SK_N, RB_SK_D, RB_SK_Z, RB_SK_CNT, RB_SK_REC, RB_SK_FRAMES, RB_SK_PIMG, RB_SK_STARTS, RB_SK_COUNTS,
+       RB_SK_OFFSETS, RB_SK_TOTAL, RB_SK_PEAKS, RB_SK_CAND, RB_COUNT };
 
 struct celeste_resid_ctx : ClientCtx<RB_COUNT, 5, 4> {
     // the tile table of every image (built once: the patches do not change), and its host mirror's offsets
@@ -412,6 +418,16 @@ struct celeste_resid_ctx : ClientCtx<RB_COUNT, 5, 4> {
     std::vector<double> taps;
     std::vector<int32_t> sample_in;
     std::vector<double> sample_out;
+    // the stack: the frames of the last search that are OK; the last stack's grid and channels; its events and times
+    std::vector<char> frame_ok;
+    bool stacked = false;
+    int32_t sk_H = 0, sk_W = 0, sk_ch = 0;
+    std::vector<StackImg> sk_imgs;
+    std::vector<double> sk_wts;
+    std::vector<PeakImg> sk_pimg;
+    std::vector<int32_t> sk_starts;
+    hipEvent_t sk_ev[3] = {};
+    float sk_ms[2] = {};
 };
 
 extern "C" int celeste_resid_version(void) { return CELESTE_RESID_ABI_VERSION; }
@@ -430,7 +446,14 @@ extern "C" int celeste_resid_ctx_create(const celeste_problem_t *problem, int de
     return client_create(problem, device, out);
 } ABI_CATCH
 
-extern "C" void celeste_resid_ctx_destroy(celeste_resid_ctx_t *f) { client_destroy(f); }
+extern "C" void celeste_resid_ctx_destroy(celeste_resid_ctx_t *f) {
+    if (f && f->c) {
+        (void)hipSetDevice(f->c->device);
+        (void)hipStreamSynchronize(f->c->stream);
+        for (auto &e : f->sk_ev) if (e) (void)hipEventDestroy(e);
+    }
+    client_destroy(f);
+}
 
 // The tile table: for every image its 32 x 8 tiles in (column of tiles, row of tiles) order, and per tile the visits whose
 // patch rectangle without its last column meets it, in ascending visit (hence source) order.  Uploaded once.
@@ -552,6 +575,7 @@ extern "C" int celeste_resid_search(celeste_resid_ctx_t *f, const double *vp, in
     const int R = opts->radius, T = 2 * R + 1, K = opts->psf_K;
     const size_t ni = (size_t)n_images;
     f->searched = false;
+    f->stacked = false;
     std::vector<ResidImg> &cimg = f->cimg;
     cimg.assign(ni, ResidImg());
     std::vector<int32_t> &starts = f->starts;                 // [3][ni + 1]: model tiles, filter tiles, peak blocks
@@ -647,6 +671,8 @@ extern "C" int celeste_resid_search(celeste_resid_ctx_t *f, const double *vp, in
         HIP_TRY(hipStreamSynchronize(st));
     }
     client_stage_ms(f);
+    f->frame_ok.assign(ni, 0);
+    for (size_t k = 0; k < ni; ++k) f->frame_ok[k] = out_frames[k].status == CELESTE_OK;
     f->searched = true;
     *n_found = total;
     for (size_t k = 0; k < ni && *status == CELESTE_OK; ++k) *status = out_frames[k].status;
@@ -741,3 +767,181 @@ extern "C" int celeste_resid_find_peaks(int device, int32_t H, int32_t W, const 
 } ABI_CATCH
 
 extern "C" int celeste_resid_last_ms(celeste_resid_ctx_t *f, float ms[4]) { return client_last_ms(f, ms); }
+
+// ---- the stack -------------------------------------------------------------------------------------------------------------------
+extern "C" void celeste_resid_stack_opts_default(celeste_resid_stack_opts_t *o) {
+    if (!o) return;
+    o->threshold = 5.0; o->min_images = 1; o->reserved = 0;
+}
+
+extern "C" int celeste_resid_wcs_check(int32_t n, const celeste_resid_wcs_t *wcs) {
+    if (n < 1 || !wcs) return CELESTE_ERR_INVALID_ARG;
+    for (int i = 0; i < n; ++i) if (!stack_wcs_ok(wcs[i])) return CELESTE_ERR_INVALID_ARG;
+    return CELESTE_OK;
+}
+
+template <int NCH>
+static void stack_launch(hipStream_t st, unsigned n_tiles, const StackGrid &g, const StackImg *d_imgs, int n_img, const double *d_wts,
+                         int n_ch, int min_images, int cull, const double *d_n, const double *d_d, const double *d_z, double *oN,
+                         double *oD, double *oZ, int32_t *oC, StackTileRec *rec) {
+    hipLaunchKernelGGL(resid_stack_kernel<NCH>, dim3(n_tiles), dim3(256), 0, st, g, d_imgs, n_img, d_wts, n_ch, min_images, cull, d_n,
+                       d_d, d_z, oN, oD, oZ, oC, rec);
+}
+
+extern "C" int celeste_resid_stack(celeste_resid_ctx_t *f, const celeste_resid_grid_t *grid, int32_t n_images,
+                                   const celeste_resid_wcs_t *wcs, int32_t n_channels, const double *weights,
+                                   const celeste_resid_stack_opts_t *opts, celeste_resid_stack_frame_t *out_frames,
+                                   celeste_resid_stack_candidate_t *out_candidates, int64_t max_candidates, int64_t *n_found,
+                                   int32_t *status) try {
+    if (!f || !f->c || !grid || !wcs || !weights || !opts || !out_frames || !n_found || !status) return CELESTE_ERR_INVALID_ARG;
+    if (!f->searched || n_images != f->c->N) return CELESTE_ERR_INVALID_ARG;
+    if (grid->H < 1 || grid->W < 1 || (int64_t)grid->H * grid->W >= (1ll << 31)) return CELESTE_ERR_INVALID_ARG;
+    if (n_channels < 1 || n_channels > SK_MAXCH || opts->min_images < 1) return CELESTE_ERR_INVALID_ARG;
+    if (max_candidates < 0 || (max_candidates > 0 && !out_candidates)) return CELESTE_ERR_INVALID_ARG;
+    for (int k = 0; k < n_channels; ++k) {
+        bool any = false;
+        for (int b = 0; b < 5; ++b) {
+            const double s = weights[k * 5 + b];
+            if (!std::isfinite(s) || s < 0.0) return CELESTE_ERR_INVALID_ARG;
+            any |= s > 0.0;
+        }
+        if (!any) return CELESTE_ERR_INVALID_ARG;
+    }
+    if (!stack_wcs_ok(grid->wcs) || celeste_resid_wcs_check(n_images, wcs) != CELESTE_OK) return CELESTE_ERR_INVALID_ARG;
+    celeste_ctx_t *c = f->c;
+    const char *nc = std::getenv("CELESTE_STACK_NO_CULL");
+    const int cull = !(nc && nc[0] == '1');
+    // the images that can add something: OK in the last search, a weight above zero in some channel; in the search's order
+    std::vector<StackImg> &imgs = f->sk_imgs;
+    imgs.clear();
+    for (size_t k = 0; k < f->cimg.size(); ++k) {
+        const ResidImg &ci = f->cimg[k];
+        const int band = c->imgs->h_images[ci.img].band;
+        if (band < 1 || band > 5) return CELESTE_ERR_INVALID_ARG;
+        bool used = false;
+        for (int ch = 0; ch < n_channels; ++ch) used |= weights[ch * 5 + band - 1] > 0.0;
+        if (!f->frame_ok[k] || !used) continue;
+        const StackWcs w = stack_wcs_dev(wcs[ci.img]);
+        StackImg im;
+        im.kind = w.kind; im.band = band; im.H = ci.H; im.W = ci.W; im.off = ci.off;
+        for (int j = 0; j < 4; ++j) im.fwd[j] = w.fwd[j];
+        for (int j = 0; j < 2; ++j) { im.w0[j] = w.w0[j]; im.p0[j] = w.p0[j]; }
+        im.sin0 = w.sin0; im.cos0 = w.cos0;
+        imgs.push_back(im);
+    }
+    StackGrid g;
+    g.H = grid->H; g.W = grid->W; g.wcs = stack_wcs_dev(grid->wcs);
+    const int H = g.H, W = g.W, nch = n_channels;
+    const int64_t HW = (int64_t)H * W;
+    const int64_t n_tiles = (int64_t)((H + SK_TH - 1) / SK_TH) * ((W + SK_TW - 1) / SK_TW);
+    const int64_t pb1 = (HW + RS_PB - 1) / RS_PB, pb = pb1 * nch;
+    f->sk_wts.assign(weights, weights + (size_t)nch * 5);
+    f->sk_pimg.assign((size_t)nch, PeakImg());
+    f->sk_starts.assign((size_t)nch + 1, 0);
+    for (int k = 0; k < nch; ++k) {
+        PeakImg &pi = f->sk_pimg[k];
+        pi.img = k; pi.H = H; pi.W = W; pi.pad = 0; pi.off = (int64_t)k * HW;
+        f->sk_starts[k + 1] = (int32_t)(pb1 * (k + 1));
+    }
+    *n_found = 0;
+    *status = CELESTE_OK;
+    HIP_TRY(hipSetDevice(c->device));
+    for (auto &e : f->sk_ev) if (!e) HIP_TRY(hipEventCreate(&e));
+    f->stacked = false;
+    StackImg *d_imgs = nullptr;
+    double *d_wts = nullptr, *oN = nullptr, *oD = nullptr, *oZ = nullptr;
+    int32_t *oC = nullptr, *d_starts = nullptr, *d_counts = nullptr;
+    StackTileRec *d_rec = nullptr;
+    celeste_resid_stack_frame_t *d_frames = nullptr;
+    PeakImg *d_pimg = nullptr;
+    int64_t *d_offsets = nullptr, *d_total = nullptr;
+    celeste_resid_candidate_t *d_peaks = nullptr;
+    celeste_resid_stack_candidate_t *d_cand = nullptr;
+    const size_t planes = (size_t)nch * (size_t)HW;
+    if (client_get(f, RB_SK_IMGS, imgs.size() * sizeof(StackImg), &d_imgs) != hipSuccess ||
+        client_get(f, RB_SK_WTS, (size_t)nch * 5 * sizeof(double), &d_wts) != hipSuccess ||
+        client_get(f, RB_SK_N, planes * sizeof(double), &oN) != hipSuccess ||
+        client_get(f, RB_SK_D, planes * sizeof(double), &oD) != hipSuccess ||
+        client_get(f, RB_SK_Z, planes * sizeof(double), &oZ) != hipSuccess ||
+        client_get(f, RB_SK_CNT, planes * sizeof(int32_t), &oC) != hipSuccess ||
+        client_get(f, RB_SK_REC, (size_t)nch * (size_t)n_tiles * sizeof(StackTileRec), &d_rec) != hipSuccess ||
+        client_get(f, RB_SK_FRAMES, (size_t)nch * sizeof(celeste_resid_stack_frame_t), &d_frames) != hipSuccess ||
+        client_get(f, RB_SK_PIMG, (size_t)nch * sizeof(PeakImg), &d_pimg) != hipSuccess ||
+        client_get(f, RB_SK_STARTS, ((size_t)nch + 1) * sizeof(int32_t), &d_starts) != hipSuccess ||
+        client_get(f, RB_SK_COUNTS, (size_t)pb * sizeof(int32_t), &d_counts) != hipSuccess ||
+        client_get(f, RB_SK_OFFSETS, (size_t)pb * sizeof(int64_t), &d_offsets) != hipSuccess ||
+        client_get(f, RB_SK_TOTAL, sizeof(int64_t), &d_total) != hipSuccess ||
+        client_get(f, RB_SK_PEAKS, (size_t)max_candidates * sizeof(celeste_resid_candidate_t), &d_peaks) != hipSuccess ||
+        client_get(f, RB_SK_CAND, (size_t)max_candidates * sizeof(celeste_resid_stack_candidate_t), &d_cand) != hipSuccess)
+        return CELESTE_ERR_HIP;
+    hipStream_t st = c->stream;
+    if (!imgs.empty()) HIP_TRY(hipMemcpyAsync(d_imgs, imgs.data(), imgs.size() * sizeof(StackImg), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(d_wts, f->sk_wts.data(), (size_t)nch * 5 * sizeof(double), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(d_pimg, f->sk_pimg.data(), (size_t)nch * sizeof(PeakImg), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(d_starts, f->sk_starts.data(), ((size_t)nch + 1) * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    const double *d_n = (const double *)f->buf[RB_N].p, *d_d = (const double *)f->buf[RB_D].p, *d_z = (const double *)f->buf[RB_Z].p;
+    HIP_TRY(hipEventRecord(f->sk_ev[0], st));
+    {
+        const unsigned nt = (unsigned)n_tiles;
+        const int ni = (int)imgs.size(), mi = opts->min_images;
+        if (nch <= 1) stack_launch<1>(st, nt, g, d_imgs, ni, d_wts, nch, mi, cull, d_n, d_d, d_z, oN, oD, oZ, oC, d_rec);
+        else if (nch <= 2) stack_launch<2>(st, nt, g, d_imgs, ni, d_wts, nch, mi, cull, d_n, d_d, d_z, oN, oD, oZ, oC, d_rec);
+        else if (nch <= 4) stack_launch<4>(st, nt, g, d_imgs, ni, d_wts, nch, mi, cull, d_n, d_d, d_z, oN, oD, oZ, oC, d_rec);
+        else stack_launch<8>(st, nt, g, d_imgs, ni, d_wts, nch, mi, cull, d_n, d_d, d_z, oN, oD, oZ, oC, d_rec);
+    }
+    hipLaunchKernelGGL(stack_zrange_kernel, dim3((unsigned)nch), dim3(256), 0, st, d_rec, (int)n_tiles, d_frames);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(f->sk_ev[1], st));
+    {
+        const int rc = resid_run_peaks(st, d_pimg, d_starts, nch, (int)pb, oZ, oN, oD, nullptr, opts->threshold, d_counts, d_offsets,
+                                       d_total, d_peaks, max_candidates);
+        if (rc != CELESTE_OK) return rc;
+    }
+    int64_t total = 0;
+    HIP_TRY(hipMemcpyAsync(out_frames, d_frames, (size_t)nch * sizeof(celeste_resid_stack_frame_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(&total, d_total, sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    const int64_t n_out = std::min(total, max_candidates);
+    if (n_out > 0) {
+        hipLaunchKernelGGL(stack_finish_kernel, dim3((unsigned)((n_out + 255) / 256)), dim3(256), 0, st, n_out, d_peaks, g, oC, d_cand);
+        HIP_TRY(hipGetLastError());
+    }
+    HIP_TRY(hipEventRecord(f->sk_ev[2], st));
+    if (n_out > 0)
+        HIP_TRY(hipMemcpyAsync(out_candidates, d_cand, (size_t)n_out * sizeof(celeste_resid_stack_candidate_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    for (int k = 0; k < 2; ++k)
+        if (hipEventElapsedTime(&f->sk_ms[k], f->sk_ev[k], f->sk_ev[k + 1]) != hipSuccess) f->sk_ms[k] = 0;
+    f->sk_H = H; f->sk_W = W; f->sk_ch = nch;
+    f->stacked = true;
+    *n_found = total;
+    if (total > max_candidates) *status = CELESTE_RESID_TRUNCATED;
+    return CELESTE_OK;
+} ABI_CATCH
+
+extern "C" int celeste_resid_stack_get_map(celeste_resid_ctx_t *f, int32_t channel, int32_t which, double *out_plane) try {
+    if (!f || !f->c || !out_plane || which < CELESTE_RESID_STACK_N || which > CELESTE_RESID_STACK_COUNT) return CELESTE_ERR_INVALID_ARG;
+    if (!f->stacked || channel < 0 || channel >= f->sk_ch) return CELESTE_ERR_INVALID_ARG;
+    static const int buf_of[4] = {RB_SK_N, RB_SK_D, RB_SK_Z, RB_SK_CNT};
+    const size_t HW = (size_t)f->sk_H * f->sk_W;
+    HIP_TRY(hipSetDevice(f->c->device));
+    hipStream_t st = f->c->stream;
+    if (which == CELESTE_RESID_STACK_COUNT) {
+        std::vector<int32_t> cnt(HW);
+        HIP_TRY(hipMemcpyAsync(cnt.data(), (const int32_t *)f->buf[RB_SK_CNT].p + (size_t)channel * HW, HW * sizeof(int32_t),
+                               hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        for (size_t i = 0; i < HW; ++i) out_plane[i] = (double)cnt[i];
+        return CELESTE_OK;
+    }
+    HIP_TRY(hipMemcpyAsync(out_plane, (const double *)f->buf[buf_of[which]].p + (size_t)channel * HW, HW * sizeof(double),
+                           hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return CELESTE_OK;
+} ABI_CATCH
+
+extern "C" int celeste_resid_stack_last_ms(celeste_resid_ctx_t *f, float ms[2]) {
+    if (!f || !ms) return CELESTE_ERR_INVALID_ARG;
+    ms[0] = f->sk_ms[0]; ms[1] = f->sk_ms[1];
+    return CELESTE_OK;
+}

@@ -306,7 +306,8 @@ def infer_box(images, box: BoundingBox, catalog=None, method: str = "joint_vi", 
               n_iters: int = NUM_JOINT_VI_ITERS, device: int = 0, schedule: str = "cyclades",
               devices: Optional[Sequence[int]] = None, match_radius: float = 1.0 / 3600.0,
               mcmc_config=None, prep: str = "host", diagnostics: bool = False, light_curves: bool = False,
-              uncertainties: bool = False, refine: int = 0, refine_threshold: float = 5.0) -> list:
+              uncertainties: bool = False, refine: int = 0, refine_threshold: float = 5.0,
+              refine_stack: bool = False) -> list:
     """infer_box / _infer_box (ParallelRun.jl:610-672): targets = catalog entries strictly inside the box, neighbours
     may lie outside it, then joint or single variational inference on the device (method in {joint_vi, single_vi}:
     one OptimizedSource per target) or MCMC (method = "mcmc": process_source_mcmc, ParallelRun.jl:504-543, with
@@ -338,7 +339,13 @@ def infer_box(images, box: BoundingBox, catalog=None, method: str = "joint_vi", 
     append those strictly inside the box to the catalog as stars, and run the catalog path again over the extended catalog with
     targets = the old targets followed by the new ones; it stops early when a round adds nothing.  Every result carries
     `refined`: the round that added its source, None for the others.  On the first device of a device group.  Not available
-    with method="mcmc".  The default loads nothing and changes nothing."""
+    with method="mcmc".  The default loads nothing and changes nothing.
+    refine_stack: each refinement round also adds the search's maps across images on a sky grid that covers the searched frames
+    within the box (resid.grid_covering, ResidualSearch.stack at refine_threshold with flat weights) and takes the stacked
+    peaks that are neither catalog sources nor what the round's single-image search already found (resid.stacked_sources):
+    the sources too faint for every single image.  Needs refine >= 1.  The default loads nothing and changes nothing."""
+    if refine_stack and not refine:
+        raise ValueError("refine_stack=True needs refine >= 1: the stack is a step of a refinement round")
     if refine and method == "mcmc":
         raise ValueError("refine needs a parameter table: method='mcmc' returns samples, not parameters")
     if refine:
@@ -346,13 +353,13 @@ def infer_box(images, box: BoundingBox, catalog=None, method: str = "joint_vi", 
         results = _infer_box_round(images, box, catalog, method, cfg, n_iters, device, schedule, devices, match_radius,
                                    mcmc_config, prep, diagnostics, light_curves, uncertainties, state)
         return _refine(images, box, results, state, int(refine), float(refine_threshold), method, cfg, n_iters, device, schedule,
-                       devices, mcmc_config, prep, diagnostics, light_curves, uncertainties)
+                       devices, mcmc_config, prep, diagnostics, light_curves, uncertainties, bool(refine_stack))
     return _infer_box_round(images, box, catalog, method, cfg, n_iters, device, schedule, devices, match_radius, mcmc_config,
                             prep, diagnostics, light_curves, uncertainties, None)
 
 
 def _refine(images, box, results, state, rounds, threshold, method, cfg, n_iters, device, schedule, devices, mcmc_config, prep,
-            diagnostics, light_curves, uncertainties) -> list:
+            diagnostics, light_curves, uncertainties, stack=False) -> list:
     """infer_box(..., refine=rounds): the loop of residual search and renewed inference.  state: what the first inference left
     (_with_fit: problem, catalog, targets, device); empty when the box held no target."""
     if not results or not state:
@@ -364,7 +371,12 @@ def _refine(images, box, results, state, rounds, threshold, method, cfg, n_iters
         vp = init_source_table(catalog)
         vp[targets] = np.stack([r.vs for r in results])
         with resid.ResidContext(problem, dev) as rc:
-            _, entries = resid.missed_sources(rc.search(vp, threshold=threshold), images, catalog)
+            search = rc.search(vp, threshold=threshold)
+            _, entries = resid.missed_sources(search, images, catalog)
+            if stack and search.images:
+                # (the stack sees what the single-image search saw too: those count as catalog sources here, so a source is added once)
+                stacked = search.stack(resid.grid_covering(images, search.images, box), threshold=threshold)
+                entries = entries + resid.stacked_sources(stacked, search, images, list(catalog) + entries)[1]
         new = [ce for ce in entries if box.contains(ce.pos)]
         if not new:
             break
