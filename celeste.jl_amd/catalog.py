@@ -140,11 +140,38 @@ def uncertainty_columns(ub, vs) -> Dict[str, Optional[float]]:
     return out
 
 
+ASTROMETRY_COLUMNS = ("n_epochs_astrom", "pm_ra", "pm_dec", "pm_ra_stderr", "pm_dec_stderr", "astrom_chi2_const",
+                      "astrom_chi2_lin")
+
+
+def astrometry_columns(am) -> Dict[str, Optional[float]]:
+    """the motion columns of one result (astrom.Astrometry of infer_box(..., astrometry=True)): the number of exposures with a
+    converged offset, the linear motion of the position in the units of pos per unit of the epochs (without a cos(dec) factor)
+    with its standard errors, and the chi-squares of the exposures' offsets about their weighted mean (2 (n - 1) degrees of
+    freedom for a source at rest) and about the linear motion (2 n - 4); None where the result carries no `astrometry` or the
+    quantity is undefined"""
+    out: Dict[str, Optional[float]] = {name: None for name in ASTROMETRY_COLUMNS}
+    if am is None:
+        return out
+
+    def num(x):
+        x = float(x)
+        return x if math.isfinite(x) else None
+    out["n_epochs_astrom"] = int(am.n_epochs[0])
+    mu, mc = am.motion[0], am.motion_cov[0]
+    out["pm_ra"], out["pm_dec"] = num(mu[0]), num(mu[1])
+    with np.errstate(invalid="ignore"):
+        out["pm_ra_stderr"], out["pm_dec_stderr"] = num(np.sqrt(mc[2, 2])), num(np.sqrt(mc[3, 3]))
+    out["astrom_chi2_const"], out["astrom_chi2_lin"] = num(am.chi2_const[0]), num(am.chi2_lin[0])
+    return out
+
+
 def celeste_to_rows(results, diagnostics: bool = False, light_curves: bool = False,
-                    uncertainties: bool = False, refined: bool = False) -> List[Dict[str, Optional[float]]]:
+                    uncertainties: bool = False, refined: bool = False, astrometry: bool = False) -> List[Dict[str, Optional[float]]]:
     """one row per OptimizedSource whose sky is not flagged bad; diagnostics: each row also gets DIAGNOSTIC_COLUMNS;
     light_curves: each row also gets LIGHT_CURVE_COLUMNS; uncertainties: each row also gets UNCERTAINTY_COLUMNS; refined: each
-    row also gets refine_round (infer_box(..., refine=k): the round of the residual search that added the source, else None)"""
+    row also gets refine_round (infer_box(..., refine=k): the round of the residual search that added the source, else None);
+    astrometry: each row also gets ASTROMETRY_COLUMNS"""
     rows = [variational_parameters_to_row(r.vs) for r in results if not r.is_sky_bad]
     if diagnostics:
         for row, r in zip(rows, [r for r in results if not r.is_sky_bad]):
@@ -158,6 +185,9 @@ def celeste_to_rows(results, diagnostics: bool = False, light_curves: bool = Fal
     if refined:
         for row, r in zip(rows, [r for r in results if not r.is_sky_bad]):
             row["refine_round"] = getattr(r, "refined", None)
+    if astrometry:
+        for row, r in zip(rows, [r for r in results if not r.is_sky_bad]):
+            row.update(astrometry_columns(getattr(r, "astrometry", None)))
     return rows
 
 

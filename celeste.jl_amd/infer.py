@@ -188,6 +188,7 @@ class OptimizedSource:
     fit: Optional[object] = None   # infer_box(..., diagnostics=True): this source's fit.FitStats at the final parameters
     light_curve: Optional[object] = None   # infer_box(..., light_curves=True): this source's phot.LightCurves (one target)
     uncertainty: Optional[object] = None   # infer_box(..., uncertainties=True): this source's info.InfoBounds (one target)
+    astrometry: Optional[object] = None   # infer_box(..., astrometry=True): this source's astrom.Astrometry (one target)
     refined: Optional[int] = None   # infer_box(..., refine=k): the round of the residual search that added this source; None: it was there from the start
 
 
@@ -307,7 +308,7 @@ def infer_box(images, box: BoundingBox, catalog=None, method: str = "joint_vi", 
               devices: Optional[Sequence[int]] = None, match_radius: float = 1.0 / 3600.0,
               mcmc_config=None, prep: str = "host", diagnostics: bool = False, light_curves: bool = False,
               uncertainties: bool = False, refine: int = 0, refine_threshold: float = 5.0,
-              refine_stack: bool = False) -> list:
+              refine_stack: bool = False, astrometry: bool = False, epochs=None) -> list:
     """infer_box / _infer_box (ParallelRun.jl:610-672): targets = catalog entries strictly inside the box, neighbours
     may lie outside it, then joint or single variational inference on the device (method in {joint_vi, single_vi}:
     one OptimizedSource per target) or MCMC (method = "mcmc": process_source_mcmc, ParallelRun.jl:504-543, with
@@ -343,19 +344,27 @@ def infer_box(images, box: BoundingBox, catalog=None, method: str = "joint_vi", 
     refine_stack: each refinement round also adds the search's maps across images on a sky grid that covers the searched frames
     within the box (resid.grid_covering, ResidualSearch.stack at refine_threshold with flat weights) and takes the stacked
     peaks that are neither catalog sources nor what the round's single-image search already found (resid.stacked_sources):
-    the sources too faint for every single image.  Needs refine >= 1.  The default loads nothing and changes nothing."""
+    the sources too faint for every single image.  Needs refine >= 1.  The default loads nothing and changes nothing.
+    astrometry: after variational inference every result also carries `astrometry`, the per-exposure offsets of its source
+    (astrom.Astrometry of one target: per image the offset and scale of its light, their covariance, a flag; per target the
+    weighted mean offset and a linear motion over `epochs`, one time per image, None: the image index;
+    include/celeste_astrom.h) at the final table, on the first device.  Not available with method="mcmc".  The default loads
+    nothing and changes nothing."""
     if refine_stack and not refine:
         raise ValueError("refine_stack=True needs refine >= 1: the stack is a step of a refinement round")
+    if astrometry and method == "mcmc":
+        raise ValueError("astrometry=True needs a parameter table: method='mcmc' returns samples, not parameters")
     if refine and method == "mcmc":
         raise ValueError("refine needs a parameter table: method='mcmc' returns samples, not parameters")
+    state: Optional[dict] = {} if (refine or astrometry) else None
+    results = _infer_box_round(images, box, catalog, method, cfg, n_iters, device, schedule, devices, match_radius, mcmc_config,
+                               prep, diagnostics, light_curves, uncertainties, state)
     if refine:
-        state: dict = {}
-        results = _infer_box_round(images, box, catalog, method, cfg, n_iters, device, schedule, devices, match_radius,
-                                   mcmc_config, prep, diagnostics, light_curves, uncertainties, state)
-        return _refine(images, box, results, state, int(refine), float(refine_threshold), method, cfg, n_iters, device, schedule,
-                       devices, mcmc_config, prep, diagnostics, light_curves, uncertainties, bool(refine_stack))
-    return _infer_box_round(images, box, catalog, method, cfg, n_iters, device, schedule, devices, match_radius, mcmc_config,
-                            prep, diagnostics, light_curves, uncertainties, None)
+        results = _refine(images, box, results, state, int(refine), float(refine_threshold), method, cfg, n_iters, device, schedule,
+                          devices, mcmc_config, prep, diagnostics, light_curves, uncertainties, bool(refine_stack))
+    if astrometry:
+        results = _with_astrometry(results, state, epochs)
+    return results
 
 
 def _refine(images, box, results, state, rounds, threshold, method, cfg, n_iters, device, schedule, devices, mcmc_config, prep,
@@ -365,6 +374,7 @@ def _refine(images, box, results, state, rounds, threshold, method, cfg, n_iters
     if not results or not state:
         return results
     from . import resid
+    final = state                      # the caller's dict: receives what the last round saw
     catalog, targets, problem, dev = list(state["catalog"]), list(state["targets"]), state["problem"], state["device"]
     added = {}
     for k in range(1, rounds + 1):
@@ -394,6 +404,7 @@ def _refine(images, box, results, state, rounds, threshold, method, cfg, n_iters
         problem = state["problem"]
     for r, t in zip(results, targets):
         r.refined = added.get(t)
+    final.update(problem=problem, catalog=catalog, targets=list(targets), device=dev)
     return results
 
 
@@ -428,6 +439,23 @@ def _infer_box_round(images, box, catalog, method, cfg, n_iters, device, schedul
                                       diagnostics, light_curves, uncertainties, state)
     return _infer_box_catalog(images, catalog, targets, method, cfg, n_iters, device, schedule, devices, mcmc_config, None,
                               diagnostics, light_curves, uncertainties, state)
+
+
+def _with_astrometry(results: list, state: dict, epochs) -> list:
+    """infer_box(..., astrometry=True): every result gets the per-exposure offsets of its source (astrom.AstromContext.offsets)
+    at the table that holds the targets' optimised rows and catalog_init_source for every other source.  state: what _with_fit
+    (or the last refinement round) saw; empty when the box held no target."""
+    if not results or not state:
+        return results
+    from .astrom import AstromContext
+    catalog, targets = state["catalog"], list(state["targets"])
+    vp = init_source_table(catalog)
+    vp[targets] = np.stack([r.vs for r in results])
+    with AstromContext(state["problem"], state["device"]) as ac:
+        am = ac.offsets(vp, targets, epochs=epochs)
+    for k, r in enumerate(results):
+        r.astrometry = am[k]
+    return results
 
 
 def _with_fit(results: list, diagnostics: bool, problem, catalog, targets, device: int, light_curves: bool = False,
