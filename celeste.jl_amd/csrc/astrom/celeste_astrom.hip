@@ -1,6 +1,6 @@
 // celeste_astrom.hip -- libceleste_astrom.so: per-exposure astrometry (include/celeste_astrom.h).
 //
-// The engine's context and evaluation code (celeste_abi.hip) is compiled into this library, unchanged, as into the fit, phot
+// The engine's context code (engine_context.h) and its kernels' header are compiled into this library, unchanged, as into the fit, phot
 // and info libraries; the context, the work list and the pixel walk (the neighbours' light B of every pixel) are
 // engine_client.h's, the densities' gradients density_grad.h's (shared with the info library).  This file adds three kernels.
 // One call:
@@ -19,7 +19,7 @@
 //                         every pass
 //   astrom_summary_kernel one lane per target: its OK entries added in image order; mean, linear motion, status
 // No floating-point atomics; every rounded operation of the sums is spelled out (no contraction).
-#include "../celeste_abi.hip"
+#include "../engine_context.h"
 #include "../engine_client.h"
 #include "../density_grad.h"
 #include "../../../include/celeste_astrom.h"

@@ -1,6 +1,6 @@
 // density_grad.h -- the two densities with their first derivatives, shared by the info and astrom libraries.
 //
-// Included after celeste_abi.hip (bspline_w, exp_nonpos, Comp, CEL_COEF).  Everything is __device__ __forceinline__: what a
+// Included after engine_context.h (bspline_w, exp_nonpos, Comp, CEL_COEF).  Everything is __device__ __forceinline__: what a
 // caller does not use of a result is dropped by the compiler, and no library's export map knows of these functions.
 #pragma once
 

@@ -1,6 +1,6 @@
 // celeste_fit.hip -- libceleste_fit.so: per-source goodness of fit (include/celeste_fit.h).
 //
-// The engine's context and evaluation code (celeste_abi.hip) is compiled into this library, unchanged: the patch table, the
+// The engine's context code (engine_context.h) and its kernels' header are compiled into this library, unchanged: the patch table, the
 // per-visit tables of prep_kernel, the spline coefficients, the bitmaps and the neighbour lists are the engine's, and the
 // two densities are its star_value and galaxy_value.  The context, the work list and the pixel walk (the target's own light m
 // and the neighbours' light B of every pixel) are engine_client.h's; this file adds two kernels.  One call:
@@ -11,7 +11,7 @@
 //                        into its band rows (lane = band x statistic) and writes its status
 // A tile is 64 consecutive pixels of a patch whatever the chunk size is (chunks are multiples of 64 pixels), so the sums do not
 // depend on it.  No floating-point atomics.
-#include "../celeste_abi.hip"
+#include "../engine_context.h"
 #include "../engine_client.h"
 #include "../../../include/celeste_fit.h"
 

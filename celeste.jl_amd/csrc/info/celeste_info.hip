@@ -1,7 +1,7 @@
 // celeste_info.hip -- libceleste_info.so: position and shape standard errors from the pixels' Fisher information
 // (include/celeste_info.h).
 //
-// The engine's context and evaluation code (celeste_abi.hip) is compiled into this library, unchanged, as into the fit and phot
+// The engine's context code (engine_context.h) and its kernels' header are compiled into this library, unchanged, as into the fit and phot
 // libraries; the context, the work list and the pixel walk (the neighbours' light B of every pixel) are engine_client.h's.
 // This file adds three kernels.  One call:
 //   prep_kernel          (the engine's) SrcImg and Comp of every visit of the context at the call's table
@@ -13,7 +13,7 @@
 //   info_solve_kernel    one thread per (target, type): Schur complement, scaling, Cholesky, inverse and flags
 // A tile is 64 consecutive pixels of a patch whatever the chunk size is, so the sums do not depend on it.  No floating-point
 // atomics.
-#include "../celeste_abi.hip"
+#include "../engine_context.h"
 #include "../engine_client.h"
 #include "../density_grad.h"
 #include "../../../include/celeste_info.h"

@@ -1,7 +1,7 @@
 // celeste_phot.hip -- libceleste_phot.so: per-exposure forced photometry (include/celeste_phot.h).
 //
-// The engine's context and evaluation code (celeste_abi.hip) is compiled into this library, unchanged, as for the fit and
-// blend libraries: the patch table, the per-visit tables of prep_kernel, the spline coefficients, the bitmaps, the neighbour
+// The engine's context code (engine_context.h) and its kernels' header are compiled into this library, unchanged, as for the
+// fit library: the patch table, the per-visit tables of prep_kernel, the spline coefficients, the bitmaps, the neighbour
 // lists, star_value and galaxy_value are the engine's.  The context, the work list and the pixel walk (the target's own light
 // m and the neighbours' light B of every pixel) are engine_client.h's; this file adds three kernels.  One call:
 //   prep_kernel          (the engine's) SrcImg and Comp of every visit of the context at the call's table
@@ -18,7 +18,7 @@
 //                        alternating between two buffers (one barrier per round).
 //   phot_summary_kernel  one wavefront per target: lane b adds the OK entries of band b in ascending image order; status
 // No floating-point atomics; every rounded operation of a pass is spelled out (no contraction), so both paths agree bit for bit.
-#include "../celeste_abi.hip"
+#include "../engine_context.h"
 #include "../engine_client.h"
 #include "../../../include/celeste_phot.h"
 

@@ -1,6 +1,6 @@
 // celeste_resid.hip -- libceleste_resid.so: whole-frame residuals and their peaks (include/celeste_resid.h).
 //
-// The engine's context and evaluation code (celeste_abi.hip) is compiled into this library, unchanged: the patch table, the
+// The engine's context code (engine_context.h) and its kernels' header are compiled into this library, unchanged: the patch table, the
 // per-visit tables of prep_kernel, the spline coefficients and the bitmaps are the engine's, and the two densities are its
 // star_value and galaxy_value.  The context, its growable buffers and the stage times are engine_client.h's.  One search:
 //   prep_kernel            (the engine's) SrcImg and Comp of every visit of the context at the call's table
@@ -17,7 +17,7 @@
 //
 // LDS of the filter: (32 + 24) x (16 + 24) doubles twice and 25 x 25 taps = 40.8 KB at the largest radius, so three
 // workgroups share a CU's 160 KB; a lane reads two LDS doubles and one tap per (tap, output) for three fp64 FMAs.
-#include "../celeste_abi.hip"
+#include "../engine_context.h"
 #include "../engine_client.h"
 #include "../../../include/celeste_resid.h"
 

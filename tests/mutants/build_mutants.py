@@ -11,7 +11,6 @@ import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
-CSRC = os.path.join(ROOT, "celeste.jl_amd", "csrc")
 MUTANTS = {1: "iota_by_column", 2: "sky_transposed", 3: "one_stamp_for_all",
            # single-precision code only (CELESTE_FLAG_FP32)
            4: "px2_h4c_dropped_term", 5: "px2_grad_nu_low_half", 6: "value_f2_p12_low_half", 7: "pk_h4b_m3p11"}
@@ -54,14 +53,13 @@ def path(k):
 
 def build(force=False):
     sys.path.insert(0, ROOT)
-    import __graft_entry__ as ge     # the product's own compile and link flags (exports.map, RCCL)
-    srcs = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hip", ".h", ".inc", ".map"))]
-    newest = max(os.path.getmtime(s) for s in srcs)
+    import __graft_entry__ as ge     # the product's own command line (exports.map, RCCL)
+    newest = max(os.path.getmtime(s) for s in ge.sources("engine"))
     procs = []
     for k in MUTANTS:
         if force or not os.path.exists(path(k)) or os.path.getmtime(path(k)) < newest:
-            procs.append(subprocess.Popen([ge.HIPCC] + ge.HIP_FLAGS + ["-DCELESTE_MUTANT=%d" % k, "-o", path(k),
-                                           os.path.join(CSRC, "celeste_abi.hip")] + ge.LINK_FLAGS, cwd=CSRC))
+            argv, cwd = ge.compile_command("engine", out=path(k), defines=["CELESTE_MUTANT=%d" % k])
+            procs.append(subprocess.Popen(argv, cwd=cwd))
     for p in procs:
         if p.wait() != 0:
             raise SystemExit("mutant build failed")
@@ -74,26 +72,18 @@ def satellite_path(entry):
 
 
 def build_satellite(force=False):
-    """the libraries of SATELLITE, in its order: each library's own source, directory, exports.map and link line, the product's
-    flags, one -D<macro>=<k>"""
+    """the libraries of SATELLITE, in its order: each library's own command line (the product's), one -D<macro>=<k>"""
     sys.path.insert(0, ROOT)
     import __graft_entry__ as ge
-    srcs = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hip", ".h", ".inc", ".map"))]
-    newest = {}
-    for lib in sorted({e[3] for e in SATELLITE}):
-        d = os.path.join(CSRC, lib)
-        own = [os.path.join(d, f) for f in os.listdir(d) if f.endswith((".hip", ".h", ".map"))]
-        newest[lib] = max(os.path.getmtime(s) for s in srcs + own)
-    link = {"fit": ge.LINK_FLAGS, "phot": ge.LINK_FLAGS, "mcmc": ["-lpthread"]}
+    newest = {lib: max(os.path.getmtime(s) for s in ge.sources(lib)) for lib in {e[3] for e in SATELLITE}}
     todo = [e for e in SATELLITE
             if force or not os.path.exists(satellite_path(e)) or os.path.getmtime(satellite_path(e)) < newest[e[3]]]
     running = []
     while todo or running:
         while todo and len(running) < MAX_COMPILERS:
             macro, k, name, lib = e = todo.pop(0)
-            d = os.path.join(CSRC, lib)
-            running.append(subprocess.Popen([ge.HIPCC] + ge.HIP_FLAGS + ["-D%s=%d" % (macro, k), "-o", satellite_path(e),
-                                             os.path.join(d, "celeste_%s.hip" % lib)] + link[lib], cwd=d))
+            argv, cwd = ge.compile_command(lib, out=satellite_path(e), defines=["%s=%d" % (macro, k)])
+            running.append(subprocess.Popen(argv, cwd=cwd))
         if running[0].wait() != 0:
             for p in running[1:]:
                 p.wait()

@@ -47,16 +47,14 @@ def test_catalogue_and_header_agree():
 
 @pytest.fixture(scope="module")
 def mutants():
-    """the mutated libraries: the library's own source, directory, exports.map and link line, the product's flags, one -D"""
+    """the mutated libraries: the library's own command line (the product's), one -D"""
     sys.path.insert(0, ROOT)
     import __graft_entry__ as ge
     os.makedirs(OUT, exist_ok=True)
-    csrc = os.path.dirname(DIR)
-    srcs = [os.path.join(csrc, f) for f in os.listdir(csrc) if f.endswith((".hip", ".h", ".inc", ".map"))]
-    srcs += [os.path.join(DIR, f) for f in os.listdir(DIR) if f.endswith((".hip", ".h", ".map"))]
-    newest = max(os.path.getmtime(s) for s in srcs)
-    procs = [subprocess.Popen([ge.HIPCC] + ge.HIP_FLAGS + ["-DCELESTE_STACK_MUTANT=%d" % k, "-o", _path(k), SOURCE] + ge.LINK_FLAGS, cwd=DIR)
-             for k in MUTANTS if not os.path.exists(_path(k)) or os.path.getmtime(_path(k)) < newest]
+    newest = max(os.path.getmtime(s) for s in ge.sources("resid"))
+    stale = [k for k in MUTANTS if not os.path.exists(_path(k)) or os.path.getmtime(_path(k)) < newest]
+    cmds = [ge.compile_command("resid", out=_path(k), defines=["CELESTE_STACK_MUTANT=%d" % k]) for k in stale]
+    procs = [subprocess.Popen(argv, cwd=cwd) for argv, cwd in cmds]
     if [p.wait() for p in procs].count(0) != len(procs):
         pytest.fail("a mutant did not build")
     return {k: _path(k) for k in MUTANTS}
