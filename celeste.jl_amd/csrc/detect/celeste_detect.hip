@@ -11,6 +11,28 @@
 //   deblend_kernel     one workgroup per component (LDS, or a global scratch for large ones): multi-threshold split
 //   scatter / moments  pixel lists per object, then fp64 moments per object with a fixed-order tree reduction
 // The host reads the counts between stages (kept pixels, components, children), so no buffer can overflow.
+//
+// CELESTE_DETECT_MUTANT=k builds the library with one deliberate bug, for tests/test_detect_mutants.py (the product is 0):
+//   1 = calibrate_kernel takes nelec by column
+//   2 = mesh_kernel: an even count's median is its upper value
+//   3 = mesh_kernel: the good-cell rule is strict
+//   4 = mesh_kernel: sigma divides by n - 1
+//   5 = mesh_final_kernel: a tie goes to the last cell
+//   6 = mesh_final_kernel: the threshold uses 1.3, not params.thresh
+//   7 = filter_kernel admits a NaN centre to the mask
+//   8 = filter_kernel: conv >= thresh
+//   9 = union_kernel drops the anti-diagonal neighbour
+//   10 = keep_kernel: size > minarea
+//   11 = the host's O.parent is the batch-wide parent index
+//   12 = deblend_kernel: a piece of any size may split its leaf
+//   13 = deblend_kernel: the level exponent is one level ahead
+//   14 = deblend_kernel: equal amplitudes go to the higher core
+//   15 = deblend_kernel: children stay in core order
+//   16 = moments_kernel: the 1/12 rule is unconditional
+//   17 = moments_kernel: segmap carries the batch-wide object index
+#ifndef CELESTE_DETECT_MUTANT
+#define CELESTE_DETECT_MUTANT 0
+#endif
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 
@@ -61,7 +83,11 @@ __global__ void calibrate_kernel(const ImgDesc *imgs, int n_img, int64_t total, 
     int64_t cm = g - d.pix_off;
     int i = (int)(cm % d.H), j = (int)(cm / d.H);
     int64_t rm = d.pix_off + (int64_t)i * d.W + j;
+#if CELESTE_DETECT_MUTANT == 1
+    cal[g] = __fsub_rn(__fdiv_rn(pix_rm[rm], nelec[d.row_off + j % d.H]), sky_rm[rm]);
+#else
     cal[g] = __fsub_rn(__fdiv_rn(pix_rm[rm], nelec[d.row_off + i]), sky_rm[rm]);
+#endif
 }
 
 // ---- background mesh ----------------------------------------------------------------------------------------------
@@ -151,7 +177,11 @@ __device__ double cell_sigma(const Cell &c, double lo, double hi, int64_t n, dou
             float v = c.cal[c.base + threadIdx.x + (int64_t)c.H * j];
             if (in_set(v, lo, hi)) { double d = (double)v - mean; q += d * d; }
         }
+#if CELESTE_DETECT_MUTANT == 4
+    return sqrt(block_sum(q, red) / (double)(n - 1));
+#else
     return sqrt(block_sum(q, red) / (double)n);
+#endif
 }
 
 // one workgroup per mesh cell: rms of the cell after iterative 3-sigma clipping around the median; good = at least
@@ -173,7 +203,11 @@ __global__ __launch_bounds__(BLOCK) void mesh_kernel(const ImgDesc *imgs, int n_
     c.base = d.pix_off + (int64_t)cx * MESH + (int64_t)d.H * cy * MESH;
     double lo = -INFINITY, hi = INFINITY;
     int64_t cnt = cell_count(c, lo, hi, red);
+#if CELESTE_DETECT_MUTANT == 3
+    bool good = 2 * cnt > (int64_t)c.ci * c.cj && cnt > 0;
+#else
     bool good = 2 * cnt >= (int64_t)c.ci * c.cj && cnt > 0;
+#endif
     double sigma = NAN;
     if (good) {
         for (int it = 0; it < 100; ++it) {
@@ -183,7 +217,11 @@ __global__ __launch_bounds__(BLOCK) void mesh_kernel(const ImgDesc *imgs, int n_
             } else {
                 double a = (double)cell_select(c, lo, hi, cnt / 2 - 1, hist, word);
                 double b = (double)cell_select(c, lo, hi, cnt / 2, hist, word);
+#if CELESTE_DETECT_MUTANT == 2
+                med = b;
+#else
                 med = (a + b) * 0.5;
+#endif
             }
             sigma = cell_sigma(c, lo, hi, cnt, red);
             double nlo = fmax(lo, med - 3.0 * sigma), nhi = fmin(hi, med + 3.0 * sigma);
@@ -239,7 +277,11 @@ __global__ void mesh_final_kernel(const ImgDesc *imgs, int n_img, const double *
         for (int e = 0; e < nc; ++e) {
             if (!good[e]) continue;
             long dx = e % d.nx - cx, dy = e / d.nx - cy, dd = dx * dx + dy * dy;
+#if CELESTE_DETECT_MUTANT == 5
+            if (best < 0 || dd <= bestd) { best = e; bestd = dd; }
+#else
             if (best < 0 || dd < bestd) { best = e; bestd = dd; }
+#endif
         }
         fixed[c] = rms[best];
     }
@@ -257,7 +299,11 @@ __global__ void mesh_final_kernel(const ImgDesc *imgs, int n_img, const double *
     sort_small(filt, nc);
     float r = (float)median_sorted(filt, nc);
     rms_out[n] = r;
+#if CELESTE_DETECT_MUTANT == 6
+    thr_out[n] = __fmul_rn(1.3f, r);
+#else
     thr_out[n] = __fmul_rn(thresh, r);
+#endif
 }
 
 // ---- filter, threshold, labelling ---------------------------------------------------------------------------------
@@ -280,7 +326,13 @@ __global__ void filter_kernel(const ImgDesc *imgs, int n_img, int64_t total, con
             acc = __dadd_rn(acc, __dmul_rn(wt, (double)v));
         }
     float c0 = cal[g];
+#if CELESTE_DETECT_MUTANT == 7
+    bool m = acc > (double)thr[n];
+#elif CELESTE_DETECT_MUTANT == 8
+    bool m = c0 == c0 && acc >= (double)thr[n];
+#else
     bool m = c0 == c0 && acc > (double)thr[n];
+#endif
     conv[g] = acc;
     par[g] = m ? (uint32_t)g : NONE;
     if (mask_rm) mask_rm[d.pix_off + (int64_t)i * d.W + j] = m ? 1 : 0;
@@ -317,6 +369,9 @@ __global__ void union_kernel(const ImgDesc *imgs, int n_img, int64_t total, uint
     const int di[4] = {-1, -1, 0, 1}, dj[4] = {0, -1, -1, -1};
     for (int t = 0; t < 4; ++t) {
         int ii = i + di[t], jj = j + dj[t];
+#if CELESTE_DETECT_MUTANT == 9
+        if (t == 3) continue;
+#endif
         if (ii < 0 || ii >= d.H || jj < 0) continue;
         uint32_t q = (uint32_t)(d.pix_off + ii + (int64_t)d.H * jj);
         if (__hip_atomic_load(&par[q], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != NONE) uf_union(par, (uint32_t)g, q);
@@ -336,7 +391,11 @@ __global__ void keep_kernel(int64_t total, const uint32_t *par, const uint32_t *
     int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (g >= total) return;
     uint32_t p = par[g];
+#if CELESTE_DETECT_MUTANT == 10
+    keep[g] = (p != NONE && size[p] > (uint32_t)minarea) ? 1 : 0;
+#else
     keep[g] = (p != NONE && size[p] >= (uint32_t)minarea) ? 1 : 0;
+#endif
 }
 
 __global__ void root_kernel(int64_t n, const uint32_t *pix, const uint32_t *par, uint32_t *root) {
@@ -438,7 +497,11 @@ __global__ __launch_bounds__(BLOCK) void deblend_kernel(
     __syncthreads();
     const double F = s_F, peak = s_peak;
     for (int lev = 1; lev < nthresh && n >= 2 * minarea; ++lev) {
+#if CELESTE_DETECT_MUTANT == 13
+        const double t = (double)thr * pow(peak / (double)thr, (double)(lev + 1) / (double)nthresh);
+#else
         const double t = (double)thr * pow(peak / (double)thr, (double)lev / (double)nthresh);
+#endif
         for (int k = tid; k < n; k += T) w.lab[k] = (w.leaf[k] >= 0 && w.c[k] > t) ? k : -1;
         __syncthreads();
         // pieces: min-label propagation with pointer jumping inside each leaf
@@ -467,12 +530,17 @@ __global__ __launch_bounds__(BLOCK) void deblend_kernel(
             for (int k = 0; k < n; ++k) { int r = w.lab[k]; if (r >= 0) { w.acc[r] += w.c[k]; w.cnt[r] += 1; } }
             const int nl = s_nleaves;
             for (int L = 0; L < nl; ++L) w.lsig[L] = 0;
+#if CELESTE_DETECT_MUTANT == 12
+            const int piece_area = 1;
+#else
+            const int piece_area = minarea;
+#endif
             for (int k = 0; k < n; ++k)
-                if (w.lab[k] == k && w.acc[k] >= cont * F && w.cnt[k] >= minarea) w.lsig[w.leaf[k]] += 1;
+                if (w.lab[k] == k && w.acc[k] >= cont * F && w.cnt[k] >= piece_area) w.lsig[w.leaf[k]] += 1;
             int next = nl, split = 0;
             for (int k = 0; k < n; ++k) {
                 w.newid[k] = -1;
-                if (w.lab[k] == k && w.lsig[w.leaf[k]] >= 2 && w.acc[k] >= cont * F && w.cnt[k] >= minarea) {
+                if (w.lab[k] == k && w.lsig[w.leaf[k]] >= 2 && w.acc[k] >= cont * F && w.cnt[k] >= piece_area) {
                     w.newid[k] = next++;
                     split = 1;
                 }
@@ -542,7 +610,11 @@ __global__ __launch_bounds__(BLOCK) void deblend_kernel(
             const double *s = w.lstat + 6 * L;
             double dx = x - s[0], dy = y - s[1];
             double amp = s[5] * exp(-0.5 * (s[2] * dx * dx + s[3] * dy * dy + s[4] * dx * dy));
+#if CELESTE_DETECT_MUTANT == 14
+            if (amp >= bamp) { bamp = amp; best = L; }
+#else
             if (amp > bamp) { bamp = amp; best = L; }
+#endif
         }
         w.cnt[k] = best;
     }
@@ -551,7 +623,11 @@ __global__ __launch_bounds__(BLOCK) void deblend_kernel(
     if (tid == 0) {
         for (int L = 0; L < K; ++L) w.newid[L] = -1;
         int r = 0;
+#if CELESTE_DETECT_MUTANT == 15
+        for (int L = 0; L < K; ++L) w.newid[L] = r++;
+#else
         for (int k = 0; k < n; ++k) if (w.newid[w.cnt[k]] < 0) w.newid[w.cnt[k]] = r++;
+#endif
         for (int q = 0; q < K; ++q) child_npix[P.start + q] = 0;
         for (int k = 0; k < n; ++k) child_npix[P.start + w.newid[w.cnt[k]]] += 1;
         nchild[p] = K;
@@ -618,7 +694,11 @@ __global__ __launch_bounds__(BLOCK) void moments_kernel(const ImgDesc *imgs, con
         double v = (double)cal[g];
         f += v; fx += v * i; fy += v * j;
         xmin = min(xmin, i); ymin = min(ymin, j); nxmax = min(nxmax, -i); nymax = min(nymax, -j);
+#if CELESTE_DETECT_MUTANT == 17
+        if (segmap_rm) segmap_rm[d.pix_off + (int64_t)i * d.W + j] = (int32_t)blockIdx.x + 1;
+#else
         if (segmap_rm) segmap_rm[d.pix_off + (int64_t)i * d.W + j] = obj_local[blockIdx.x] + 1;
+#endif
     }
     f = block_sum(f, red); fx = block_sum(fx, red); fy = block_sum(fy, red);
     xmin = block_min_i(xmin, ired); ymin = block_min_i(ymin, ired);
@@ -644,7 +724,11 @@ __global__ __launch_bounds__(BLOCK) void moments_kernel(const ImgDesc *imgs, con
         r.xmin = xmin; r.xmax = -nxmax; r.ymin = ymin; r.ymax = -nymax;
         r.x = xm; r.y = ym; r.x2 = x2; r.y2 = y2; r.xy = xy; r.flux = f; r.peak = pk;
         double mx2 = x2, my2 = y2;
+#if CELESTE_DETECT_MUTANT == 16
+        { mx2 += 1.0 / 12.0; my2 += 1.0 / 12.0; }
+#else
         if (mx2 * my2 - xy * xy < 1.0 / 144.0) { mx2 += 1.0 / 12.0; my2 += 1.0 / 12.0; }
+#endif
         double tmp = mx2 - my2;
         r.theta = fabs(tmp) > 0.0 ? atan2(2.0 * xy, tmp) / 2.0 : M_PI / 4.0;
         tmp = sqrt(0.25 * tmp * tmp + xy * xy);
@@ -878,7 +962,11 @@ int run(int32_t device, int32_t n_img, const celeste_detect_image_t *images, con
             const int32_t np = cnpix[parents[p].start + r];
             objs.push_back(ObjDesc{opos, np, img});
             obj_local.push_back(n_obj_img[img]++);
+#if CELESTE_DETECT_MUTANT == 11
+            obj_parent.push_back(p);
+#else
             obj_parent.push_back(par_local[p]);
+#endif
             opos += np;
         }
     }

@@ -15,6 +15,28 @@
 //   prep_object_ranges_kernel, prep_entry_kernel, prep_detected_geometry_kernel -- then the stages above from the compaction on
 // Scans and sorts are hipCUB's (integer keys: a stable radix sort, results do not depend on the launch geometry).
 // The file is compiled with -ffp-contract=off.
+//
+// CELESTE_PREP_MUTANT=k builds the library with one deliberate bug, for tests/test_prep_mutants.py (the product is 0;
+// 17 and up are in prep_detected.h):
+//   1 = round_even rounds halves away from zero
+//   2 = clamped_box: the last column is clamped to W - 1
+//   3 = prep_geometry_kernel: the tried test takes pc1 > reach for pc1 > -reach
+//   4 = the radius takes max(pdf_90, epsilon / (20 flux))
+//   5 = the radius drops the width scale 1.2
+//   6 = pix_to_world does not pivot
+//   7 = jacobian_at takes the smaller step
+//   8 = prep_active_kernel counts NaN
+//   9 = prep_nbr_kernel: the overlap test is strict in the rows
+//   10 = prep_nbr_kernel: the row window is one short
+//   11 = prep_unique_kernel keeps repeats
+//   12 = prep_stamp_kernel: tx without the - 1
+//   13 = prep_stamp_kernel: i and j swapped in cmat
+//   14 = prep_sky_kernel: an even count's median is its upper value
+//   15 = prep_sky_kernel: claimed + 5 <= median
+//   16 = prep_sky_kernel takes nelec by column
+#ifndef CELESTE_PREP_MUTANT
+#define CELESTE_PREP_MUTANT 0
+#endif
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 #include <algorithm>
@@ -50,7 +72,11 @@ struct PrepConsts { double c1, c2, c3; };   // exp(-0.5 * 1.64^2), sqrt(2 pi), 0
 
 // rint, kept inside the int32 range (a box that far away clamps to the same empty range)
 __device__ __forceinline__ int32_t round_even(double x) {
+#if CELESTE_PREP_MUTANT == 1
+    double r = round(x);
+#else
     double r = rint(x);
+#endif
     r = r < -2.0e9 ? -2.0e9 : (r > 2.0e9 ? 2.0e9 : r);
     return (int32_t)r;
 }
@@ -94,7 +120,11 @@ __device__ __forceinline__ void world_to_pix(const PrepImg &im, double x, double
 __device__ __forceinline__ void pix_to_world(const PrepImg &im, double c1, double c2, double &w1, double &w2) {
     if (im.kind == CELESTE_PREP_WCS_TAN) { tan_pix_to_world(im, c1, c2, w1, w2); return; }
     double a11 = im.J11, a12 = im.J12, a21 = im.J21, a22 = im.J22, b1 = c1 - im.p0[0], b2 = c2 - im.p0[1];
+#if CELESTE_PREP_MUTANT == 6
+    if (false) {
+#else
     if (fabs(a21) > fabs(a11)) {
+#endif
         double t = a11; a11 = a21; a21 = t;
         t = a12; a12 = a22; a22 = t;
         t = b1; b1 = b2; b2 = t;
@@ -112,7 +142,11 @@ __device__ __forceinline__ int4 clamped_box(const PrepImg &im, double pc1, doubl
     b.x = clampi(round_even(pc1 - r), 1, im.H + 1);
     b.y = clampi(round_even(pc1 + r), 0, im.H);
     b.z = clampi(round_even(pc2 - r), 1, im.W + 1);
+#if CELESTE_PREP_MUTANT == 2
+    b.w = clampi(round_even(pc2 + r), 0, im.W - 1);
+#else
     b.w = clampi(round_even(pc2 + r), 0, im.W);
+#endif
     return b;
 }
 
@@ -126,20 +160,32 @@ __global__ void __launch_bounds__(PREP_BLOCK) prep_geometry_kernel(const PrepImg
     const celeste_prep_source_t &S = src[s];
     double pc1, pc2;
     world_to_pix(im, S.pos[0], S.pos[1], pc1, pc2);
+#if CELESTE_PREP_MUTANT == 3
+    const bool tried = dense || (pc1 > reach && pc1 < (double)(im.H + 1) + reach && pc2 > -reach && pc2 < (double)(im.W + 1) + reach);
+#else
     const bool tried = dense || (pc1 > -reach && pc1 < (double)(im.H + 1) + reach && pc2 > -reach && pc2 < (double)(im.W + 1) + reach);
+#endif
     if (!tried) { keep[p] = 0; pbox[p] = make_int4(1, 0, 1, 0); return; }
     double r = radius_override;
     // (a TAN image: pixel coordinates that are not finite are no error, the pair gets the empty box below)
     const bool off_plane = im.kind == CELESTE_PREP_WCS_TAN && !(fabs(pc1) < INFINITY && fabs(pc2) < INFINITY);
     bool bad = !off_plane && (!(pc1 == pc1) || !(pc2 == pc2));
     if (r != r) {     // choose_patch_radius, width_scale 1.2, max_radius 25
+#if CELESTE_PREP_MUTANT == 5
+        double ow = S.is_star ? 0.0 : S.gal_radius_px / 0.67;
+#else
         double ow = S.is_star ? 0.0 : 1.2 * S.gal_radius_px / 0.67;
+#endif
         ow += im.psf_width;
         const double f = S.flux[im.band - 1];
         if (!(f > 0.0)) bad = true;
         const double p90 = C.c1 / (C.c2 * ow);
         const double pe = im.eps / (20.0 * f);
+#if CELESTE_PREP_MUTANT == 4
+        const double pt = pe > p90 ? pe : p90;
+#else
         const double pt = pe < p90 ? pe : p90;                 // min(pdf_90, epsilon / (20 flux))
+#endif
         const double rhs = (log(pt) + C.c3) + log(ow);
         const double rq = sqrt((-2.0 * (ow * ow)) * rhs);
         r = 25.0 < rq ? 25.0 : rq;                             // min(radius_req, max_radius)
@@ -188,7 +234,11 @@ __device__ __forceinline__ void jacobian_at(const PrepImg &im, double c1, double
     double s1, s2, a1, a2, b1, b2;
     tan_pix_to_world(im, c1 + 0.5, c2 + 0.5, s1, s2);
     const double t1 = fabs(s1 - w1), t2 = fabs(s2 - w2);
+#if CELESTE_PREP_MUTANT == 7
+    const double t = t1 < t2 ? t1 : t2;
+#else
     const double t = t1 > t2 ? t1 : t2;
+#endif
     tan_world_to_pix(im, w1 + t, w2, a1, a2);
     tan_world_to_pix(im, w1, w2 + t, b1, b2);
     J[0] = (a1 - c1) / t; J[1] = (a2 - c2) / t; J[2] = (b1 - c1) / t; J[3] = (b2 - c2) / t;
@@ -214,14 +264,19 @@ __global__ void __launch_bounds__(PREP_BLOCK) prep_active_kernel(const PrepImg *
     const int4 b = ebox[e];
     const int nh = max(b.y - b.x + 1, 0), nw = max(b.w - b.z + 1, 0);
     int cnt = 0;
+#if CELESTE_PREP_MUTANT == 8
+    const int nan_counts = 1;
+#else
+    const int nan_counts = 0;
+#endif
     if (nh > 0 && nw > 0) {
         const float *base = im.pix + (int64_t)(b.x - 1) * im.sh + (int64_t)(b.z - 1) * im.sw;
         if (im.sw == 1) {
             for (int h = 0; h < nh; ++h)
-                for (int w = lane; w < nw; w += 64) { const float v = base[(int64_t)h * im.sh + w]; cnt += (v == v) ? 1 : 0; }
+                for (int w = lane; w < nw; w += 64) { const float v = base[(int64_t)h * im.sh + w]; cnt += (v == v) ? 1 : nan_counts; }
         } else {
             for (int w = 0; w < nw; ++w)
-                for (int h = lane; h < nh; h += 64) { const float v = base[(int64_t)h * im.sh + (int64_t)w * im.sw]; cnt += (v == v) ? 1 : 0; }
+                for (int h = lane; h < nh; h += 64) { const float v = base[(int64_t)h * im.sh + (int64_t)w * im.sw]; cnt += (v == v) ? 1 : nan_counts; }
         }
     }
     for (int d = 32; d > 0; d >>= 1) cnt += __shfl_down(cnt, d, 64);
@@ -257,7 +312,11 @@ __global__ void __launch_bounds__(PREP_BLOCK) prep_nbr_kernel(const unsigned lon
     if ((k >> 32) >= (unsigned long long)N) { if (!raw) cnt[e] = 0; return; }
     const int4 b = sbox[i];
     const unsigned long long hi32 = k & 0xffffffff00000000ull;
+#if CELESTE_PREP_MUTANT == 10
+    const int64_t first = max((int64_t)b.x - max_rows + 2, (int64_t)0);
+#else
     const int64_t first = max((int64_t)b.x - max_rows + 1, (int64_t)0);
+#endif
     const int64_t lo = lower_bound_u64(key, E, hi32 | (unsigned long long)first);
     const int64_t hi = lower_bound_u64(key, E, hi32 | (unsigned long long)((int64_t)b.y + 1));
     int64_t c = 0;
@@ -265,7 +324,11 @@ __global__ void __launch_bounds__(PREP_BLOCK) prep_nbr_kernel(const unsigned lon
     for (int64_t j = lo; j < hi; ++j) {
         if (j == i) continue;
         const int4 o = sbox[j];
+#if CELESTE_PREP_MUTANT == 9
+        if (o.y > b.x && o.z <= b.w && b.z <= o.w) {
+#else
         if (o.y >= b.x && o.z <= b.w && b.z <= o.w) {     // (o.x <= b.y by the range)
+#endif
             if (raw) raw[at + c] = ssrc[j];
             ++c;
         }
@@ -296,7 +359,11 @@ __global__ void __launch_bounds__(PREP_BLOCK) prep_unique_kernel(const int32_t *
     int64_t c = 0;
     const int64_t at = out ? noff[s] : 0;
     for (int32_t i = a; i < b; ++i)
+#if CELESTE_PREP_MUTANT == 11
+        if (true) {
+#else
         if (i == a || sorted[i] != sorted[i - 1]) {
+#endif
             if (out) out[at + c] = sorted[i];
             ++c;
         }
@@ -312,12 +379,20 @@ __global__ void __launch_bounds__(PREP_BLOCK) prep_stamp_kernel(const PrepImg *i
     const int nk = im.nk;
     if ((int)threadIdx.x < nk) {
         const int k = threadIdx.x;
+#if CELESTE_PREP_MUTANT == 12
+        const double tx = 0.001 * pc[2 * e], ty = 0.001 * (pc[2 * e + 1] - 1.0);
+#else
         const double tx = 0.001 * (pc[2 * e] - 1.0), ty = 0.001 * (pc[2 * e + 1] - 1.0);
+#endif
         double acc = 0.0, px = 1.0;
         for (int i = 0; i < im.ni; ++i) {
             double py = 1.0;
             for (int j = 0; j < im.nj; ++j) {
+#if CELESTE_PREP_MUTANT == 13
+                acc += im.cmat[((int64_t)j * im.ni + i) * nk + k] * (px * py);
+#else
                 acc += im.cmat[((int64_t)i * im.nj + j) * nk + k] * (px * py);
+#endif
                 py *= ty;
             }
             px *= tx;
@@ -411,12 +486,24 @@ __global__ void __launch_bounds__(PREP_BLOCK) prep_sky_kernel(const PrepImg *img
     float med = sky_select(vals, tot, k, hist, word);
     if ((n & 1) == 0) {
         const float lo = sky_select(vals, tot, k - 1, hist, word);
+#if CELESTE_PREP_MUTANT == 14
+        med = lo < med ? med : lo;
+#else
         med = (lo + med) * 0.5f;
+#endif
     }
     if (threadIdx.x == 0) {
         const int h = clampi(round_even(pc1), 1, im.H), w = clampi(round_even(pc2), 1, im.W);
+#if CELESTE_PREP_MUTANT == 16
+        const double claimed = (double)im.sky[(int64_t)(h - 1) * im.ksh + (int64_t)(w - 1) * im.ksw] * (double)im.nelec[min(w, im.H) - 1];
+#else
         const double claimed = (double)im.sky[(int64_t)(h - 1) * im.ksh + (int64_t)(w - 1) * im.ksw] * (double)im.nelec[h - 1];
+#endif
+#if CELESTE_PREP_MUTANT == 15
+        flags[i] = (claimed + 5.0 <= (double)med) ? 1 : 0;
+#else
         flags[i] = (claimed + 5.0 < (double)med) ? 1 : 0;
+#endif
     }
 }
 

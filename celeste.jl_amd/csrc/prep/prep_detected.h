@@ -12,6 +12,14 @@
 //   prep_entry_kernel                one thread per object: fluxes and shape of its catalog entry, its (image, object) list
 //   prep_detected_geometry_kernel    one thread per (object, image) pair: the detection box or the minimum box, clamped
 // The search of the match kernel is exhaustive: every detection of a later image against every joined entry.
+//
+// CELESTE_PREP_MUTANT (celeste_prep.hip lists 1 to 16):
+//   17 = prep_match_kernel joins at best <= match_radius
+//   18 = prep_match_kernel: the highest index among equal distances
+//   19 = prep_append_kernel appends a block's unmatched detections in reverse order
+//   20 = prep_entry_kernel: the last band on a tie gives the shape
+//   21 = prep_detected_geometry_kernel: the detection's box replaces the minimum box instead of being enclosed with it
+//   22 = prep_match_angular_kernel compares half the separation with match_radius
 #pragma once
 
 #define PREP_TILE CELESTE_PREP_MATCH_TILE
@@ -58,11 +66,19 @@ __global__ void __launch_bounds__(PREP_BLOCK) prep_match_kernel(const double2 *w
             for (int k = 0; k < m; ++k) {
                 const double dx = tile[k].x - w.x, dy = tile[k].y - w.y;
                 const double d = sqrt(dx * dx + dy * dy);
+#if CELESTE_PREP_MUTANT == 18
+                if (d <= best) { best = d; bi = t0 + k; }
+#else
                 if (d < best) { best = d; bi = t0 + k; }      // strict: the lowest index among equal distances
+#endif
             }
         __syncthreads();
     }
+#if CELESTE_PREP_MUTANT == 17
+    if (live) jidx[first + i] = (bi >= 0 && best <= match_radius) ? bi : -1;
+#else
     if (live) jidx[first + i] = (bi >= 0 && best < match_radius) ? bi : -1;
+#endif
 }
 
 struct PrepUnit { double x, y, z; };      // (cos dec cos ra, cos dec sin ra, sin dec)
@@ -106,7 +122,11 @@ __global__ void __launch_bounds__(PREP_BLOCK) prep_match_angular_kernel(const Pr
     }
     if (live) {
         const double h = best / 2.0;
+#if CELESTE_PREP_MUTANT == 22
+        const double sep = asin(h < 1.0 ? h : 1.0) * PREP_R2D;
+#else
         const double sep = 2.0 * (asin(h < 1.0 ? h : 1.0) * PREP_R2D);
+#endif
         jidx[first + i] = (bi >= 0 && sep < match_radius) ? bi : -1;
     }
 }
@@ -125,7 +145,11 @@ __global__ void __launch_bounds__(PREP_BLOCK) prep_append_kernel(const double2 *
         Scan(tmp).ExclusiveSum(flag, ex, tot);
         __syncthreads();
         if (flag) {
+#if CELESTE_PREP_MUTANT == 19
+            const int k = base + run + (tot - 1 - ex);
+#else
             const int k = base + run + ex;
+#endif
             jidx[first + i] = k;
             jpos[k] = world[first + i];
             if (unit) junit[k] = unit[first + i];
@@ -167,7 +191,11 @@ __global__ void __launch_bounds__(PREP_BLOCK) prep_entry_kernel(const PrepImg *i
     int bb = 0;
     for (int b = 0; b < 5; ++b) {
         O.flux[5 * s + b] = best[b] >= 0 ? det[best[b]].flux : 0.0;
+#if CELESTE_PREP_MUTANT == 20
+        if (npix[b] >= npix[bb]) bb = b;
+#else
         if (npix[b] > npix[bb]) bb = b;                       // the first band on a tie
+#endif
     }
     const int32_t d = best[bb];                               // (an object has a detection, and npix > 0)
     const double a = det[d].a, b = det[d].b;
@@ -183,7 +211,11 @@ __device__ __forceinline__ void dilate_enclose(int32_t first, int32_t last, doub
     const double len = (double)((int64_t)last - first + 1);
     const int64_t delta = (int64_t)round_even((dilate * len) / 2.0);
     const int32_t lo = clamp_i64((int64_t)first - delta), hi = clamp_i64((int64_t)last + delta);
+#if CELESTE_PREP_MUTANT == 21
+    m0 = lo;
+#else
     m0 = lo < m0 ? lo : m0;
+#endif
     m1 = hi > m1 ? hi : m1;
 }
 

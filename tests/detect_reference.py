@@ -19,14 +19,15 @@ def calibrate(pixels, sky, nelec):
     return (np.asarray(pixels, np.float32) / np.asarray(nelec, np.float32)[:, None]) - np.asarray(sky, np.float32)
 
 
-def cell_rms(vals):
-    """kappa-sigma clipping at 3 sigma around the median until no value leaves (at most 100 passes); fp64"""
+def cell_rms(vals, median=np.median):
+    """kappa-sigma clipping at 3 sigma around the median until no value leaves (at most 100 passes); fp64.  `median`: for
+    the scenes' own tests, which show that another median rule gives another rms"""
     v = vals[~np.isnan(vals)].astype(np.float64)
     lo, hi = -np.inf, np.inf
     s = v
     sigma = float("nan")
     for it in range(100):
-        med = float(np.median(s))
+        med = float(median(s))
         mean = s.sum() / s.size
         sigma = math.sqrt(((s - mean) ** 2).sum() / s.size)
         nlo, nhi = max(lo, med - 3.0 * sigma), min(hi, med + 3.0 * sigma)
@@ -104,14 +105,17 @@ def _pieces(ii, jj, sel):
     return lab[ii[sel] - i0, jj[sel] - j0]
 
 
-def deblend(ii, jj, c, thr, nthresh=32, cont=0.005, minarea=5):
+def deblend(ii, jj, c, thr, nthresh=32, cont=0.005, minarea=5, trace=None):
     """multi-threshold deblending of one component; pixels in raster order.  Returns the child index of every pixel
-    (children ordered by their smallest raster index)."""
+    (children ordered by their smallest raster index).  trace: a list that receives what the scenes' own tests ask about a
+    parent that splits: the levels at which a leaf split, each pixel's core (-1: none), its owner among the cores, and the
+    Gaussian amplitudes of every pixel outside the cores."""
     n = c.size
     leaf = np.zeros(n, int)
     F = seqsum(c)
     peak = float(c.max())
     next_id = 1
+    split_levels = []
     if n >= 2 * minarea:
         for lev in range(1, nthresh):
             t = float(thr) * (peak / float(thr)) ** (lev / nthresh)
@@ -128,6 +132,7 @@ def deblend(ii, jj, c, thr, nthresh=32, cont=0.005, minarea=5):
                     if seqsum(c[members]) >= cont * F and members.size >= minarea:
                         sig.append(members)
                 if len(sig) >= 2:
+                    split_levels.append((lev, int(L)))
                     new_leaf[leaf == L] = -1
                     for members in sorted(sig, key=lambda m: m[0]):
                         new_leaf[members] = next_id
@@ -150,12 +155,16 @@ def deblend(ii, jj, c, thr, nthresh=32, cont=0.005, minarea=5):
         cxx, cyy, cxy = _ellipse_coeffs(seqsum(v * dx * dx) / f, seqsum(v * dy * dy) / f, seqsum(v * dx * dy) / f)
         gauss.append((xm, ym, cxx, cyy, cxy, float(v.max())))
     owner = core.copy()
+    all_amps = {}
     for k in np.nonzero(core < 0)[0]:
         amps = []
         for (xm, ym, cxx, cyy, cxy, pk) in gauss:
             dx, dy = ii[k] - xm, jj[k] - ym
             amps.append(pk * math.exp(-0.5 * (cxx * dx * dx + cyy * dy * dy + cxy * dx * dy)))
         owner[k] = int(np.argmax(amps))
+        all_amps[(int(ii[k]), int(jj[k]))] = amps
+    if trace is not None:
+        trace.append(dict(first=(int(ii[0]), int(jj[0])), split_levels=split_levels, core=core, owner=owner.copy(), amps=all_amps))
     order = []
     for o in owner:
         if o not in order:
@@ -181,8 +190,8 @@ def moments(ii, jj, v):
                 flux=f, peak=float(v.max()))
 
 
-def extract(pixels, sky, nelec, thresh=1.3, minarea=5, nthresh=32, cont=0.005, thr=None):
-    """one image; thr (the absolute threshold) overrides the one derived from this restatement's rms"""
+def extract(pixels, sky, nelec, thresh=1.3, minarea=5, nthresh=32, cont=0.005, thr=None, trace=None):
+    """one image; thr (the absolute threshold) overrides the one derived from this restatement's rms; trace: see deblend"""
     cal = calibrate(pixels, sky, nelec)
     H, W = cal.shape
     rms = global_rms(cal)
@@ -207,7 +216,7 @@ def extract(pixels, sky, nelec, thresh=1.3, minarea=5, nthresh=32, cont=0.005, t
         parents.append((int(cm[order[0]]), ii[order], jj[order]))
     parents.sort(key=lambda p: p[0])
     for p, (_, ii, jj) in enumerate(parents):
-        child = deblend(ii, jj, conv[ii, jj], thr, nthresh, cont, minarea)
+        child = deblend(ii, jj, conv[ii, jj], thr, nthresh, cont, minarea, trace)
         for r in range(child.max() + 1):
             m = child == r
             o = moments(ii[m], jj[m], cal[ii[m], jj[m]])
@@ -215,7 +224,7 @@ def extract(pixels, sky, nelec, thresh=1.3, minarea=5, nthresh=32, cont=0.005, t
                      ymax=int(jj[m].max()), parent=p, pixels=np.stack([ii[m], jj[m]], axis=1))
             objs.append(o)
             segmap[ii[m], jj[m]] = len(objs)
-    return dict(rms=rms, thresh=thr, mask=mask, segmap=segmap, objects=objs)
+    return dict(rms=rms, thresh=thr, mask=mask, segmap=segmap, objects=objs, conv=conv)
 
 
 # ---- detect_sources ----------------------------------------------------------------------------------------------

@@ -17,8 +17,12 @@ def _close(a, b, rtol, scale=0.0):
     return abs(a - b) <= rtol * max(abs(b), scale)
 
 
-def _compare(cat, ref):
+def _compare(cat, ref, thresh=1.3):
+    """ref["rms"] is the restatement's own, whatever threshold it was given: the device's threshold is compared with the
+    one that follows from it, float32(thresh) * float32(rms) rounded to float32, bit for bit"""
     assert _close(cat.rms, ref["rms"], 1e-9) or (np.isnan(cat.rms) and np.isnan(ref["rms"]))
+    own = float(np.float32(np.float32(thresh) * np.float32(ref["rms"])))
+    assert cat.thresh == own or (np.isnan(cat.thresh) and np.isnan(own)), (cat.thresh, own)
     np.testing.assert_array_equal(cat.mask, ref["mask"])
     np.testing.assert_array_equal(cat.segmap, ref["segmap"])
     assert len(cat) == len(ref["objects"])

@@ -73,6 +73,23 @@ def join_scene():
     return images, cats
 
 
+TIE_RADIUS = 6.0
+
+
+def tie_scene():
+    """Three 60 x 60 images in bands 3, 2, 1 on one grid, every coordinate an integer, so that both the host's np.hypot and the
+    device's sqrt(dx dx + dy dy) are exact; match_radius 6.
+    image 0: entries 0 (10, 10), 1 (16, 18), 2 (40, 40).
+    image 1: detection 0 at (13, 14) lies exactly 5 from entries 0 and 1: the lower index takes it; detection 1 at (40, 46) lies
+      exactly 6 = match_radius from entry 2: not closer than the radius, so it is appended (entry 3).
+    image 2: detection 0 at (40, 43) lies 3 from entries 2 and 3 alike: entry 2 takes it."""
+    images = _images((3, 2, 1), 60, 60, 15)
+    cats = [make_catalog([_row(1, 10.0, 10.0, 20), _row(2, 16.0, 18.0, 12), _row(3, 40.0, 40.0, 9)]),
+            make_catalog([_row(4, 13.0, 14.0, 15), _row(5, 40.0, 46.0, 8)]),
+            make_catalog([_row(6, 40.0, 43.0, 11)])]
+    return images, cats
+
+
 def rotate(images):
     c, s = math.cos(0.3), math.sin(0.3)
     for im in images:
@@ -181,11 +198,17 @@ def assert_join_margin(worlds, joined, detections, match_radius):
     return checked
 
 
-def host_path(images, cats, match_radius):
+def host_path(images, cats, match_radius, exact_distances=False):
+    """exact_distances: the scene's world coordinates are integers, so its distances are exact on both sides and may be equal
+    to one another and to match_radius: asserted in place of the margin"""
     from celeste_jl_amd import detect, model
     worlds = [detect.world_coords(c, im) for c, im in zip(cats, images)]
     joined, detections = detect.match_detections(worlds, match_radius)
-    checked = assert_join_margin(worlds, joined, detections, match_radius)
+    if exact_distances:
+        assert all((np.asarray(w) == np.rint(w)).all() and np.abs(w).max(initial=0) < 2 ** 20 for w in worlds)
+        checked = 0
+    else:
+        checked = assert_join_margin(worlds, joined, detections, match_radius)
     catalog, patches = detect.build_detection_output(images, cats, match_radius)
     return dict(worlds=worlds, joined=joined, detections=detections, checked=checked, catalog=catalog, patches=patches,
                 neighbors=model.neighbor_map(patches) if patches else [])
@@ -291,6 +314,21 @@ def test_join_rules_and_catalog_entries_on_hand_made_catalogs():
     # no detection at all: zero objects, an empty table
     catalog, table = prep.detected_table(images, [make_catalog([]) for _ in images], JOIN_RADIUS)
     assert catalog == [] and table.n_sources == 0 and len(table.source) == 0 and table.neighbor_lists == [] and table.detections == []
+
+
+def test_exact_ties_of_the_join():
+    """equal distances go to the lower index; a distance equal to match_radius does not join"""
+    from celeste_jl_amd import prep
+    images, cats = tie_scene()
+    want = host_path(images, cats, TIE_RADIUS, exact_distances=True)
+    # the scene holds what it was built for
+    w = want["worlds"]
+    assert np.hypot(*(w[1][0] - w[0][0])) == np.hypot(*(w[1][0] - w[0][1])) == 5.0 < TIE_RADIUS
+    assert np.hypot(*(w[1][1] - w[0][2])) == TIE_RADIUS
+    assert np.hypot(*(w[2][0] - w[0][2])) == np.hypot(*(w[2][0] - w[1][1])) == 3.0
+    assert want["detections"] == [[(0, 0), (1, 0)], [(0, 1)], [(0, 2), (2, 0)], [(1, 1)]]
+    catalog, table = prep.detected_table(images, cats, TIE_RADIUS)
+    assert_is_host_path(images, cats, TIE_RADIUS, catalog, table, want)
 
 
 # ---- 2: past one tile, past one workgroup ------------------------------------------------------------------------------------

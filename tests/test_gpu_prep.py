@@ -150,13 +150,34 @@ def test_world_center_under_a_rotated_jacobian(scene):
     """J = rotation(0.3) diag(0.8, 1.3): the device's LU against Image.pix_to_world within the backward-error bound of a
     2 x 2 solve with partial pivoting, 8 eps cond(J) (|pixel_center - pix0|_inf |J^-1|_inf + |world0|_inf) per component
     (the factor 8 covers the different operation order; no bit equality with LAPACK)"""
-    from celeste_jl_amd import prep, synthetic
-    images, catalog = scene
+    _world_centers_under(scene, rotated_image(0.3))
+
+
+def rotated_image(angle):
+    """56 x 60 under J = rotation(angle) diag(0.8, 1.3)"""
+    from celeste_jl_amd import synthetic
     img = synthetic.blank_images(56, 60)[1]
-    c, s = math.cos(0.3), math.sin(0.3)
+    c, s = math.cos(angle), math.sin(angle)
     img.wcs_jacobian = np.array([[c, -s], [s, c]]) @ np.diag([0.8, 1.3])
     img.wcs_world0 = np.array([-3.5, 7.25])
     img.wcs_pix0 = np.array([4.0, -6.0])
+    return img
+
+
+PIVOT_ANGLE = math.pi / 2 - 1.0e-7
+
+
+def test_world_center_under_a_jacobian_that_needs_pivoting(scene):
+    """a rotation 1e-7 short of a quarter turn: |J21| = 0.8 against |J11| = 8e-8, so the rows are exchanged; without the
+    exchange the multiplier J21 / J11 is 1e7 and the solve loses seven digits, far outside the same bound"""
+    img = rotated_image(PIVOT_ANGLE)
+    assert 0 < abs(img.wcs_jacobian[0, 0]) < 1e-6 * abs(img.wcs_jacobian[1, 0])
+    _world_centers_under(scene, img)
+
+
+def _world_centers_under(scene, img):
+    from celeste_jl_amd import prep
+    images, catalog = scene
     four = list(images) + [img]
     for sparse in (False, True):
         got = prep.patch_table(four, catalog, sparse=sparse)
@@ -252,7 +273,9 @@ def test_stamps_are_the_psf_maps_within_the_dot_product_bound(sparse):
 def sky_scene():
     """A 120 x 130 band-4 image over a band-2 one, pixels around the claimed sky with a slope along the rows, and positions:
     boxes clipped at every border, an odd and an even number of valid pixels, a box that is all NaN, an empty box, two whose
-    sky was set so that claimed + 5 lies just below and just above the median, and 64 random ones."""
+    sky was set so that claimed + 5 lies just below and just above the median, three hand-made ones (an even count whose two
+    middle values lie 20 apart with claimed + 5 between their mean and the upper one; claimed + 5 equal to the median bit for
+    bit; a row whose nelec_per_nmgy differs from that of the row with the column's index), and 64 random ones."""
     from celeste_jl_amd import infer, synthetic
     rng = np.random.Generator(np.random.PCG64(4))
     images = [synthetic.blank_images(120, 130)[1], synthetic.blank_images(120, 130)[3]]
@@ -267,7 +290,19 @@ def sky_scene():
            (60.3, 65.2), (58.4, 64.7),                                                            # interior: 101 x 101
            (-45.0, -45.0),                                                                        # all NaN
            (-80.0, 40.0), (300.0, 300.0),                                                         # empty
-           (40.2, 50.3), (80.3, 70.4)]                                                            # claimed + 5 just below / above
+           (40.2, 50.3), (80.3, 70.4),                                                            # claimed + 5 just below / above
+           (-46.0, 176.0), (166.0, -46.0), (100.3, 30.2)]                                         # 13, 14, 15: see below
+    # 13: rows 1..4, columns 126..130: 20 valid pixels, the middle two at claimed - 8 and claimed + 12
+    img.pixels[0:4, 125:130] = (claimed + np.concatenate([-8.0 - np.arange(10), 12.0 + np.arange(10)])).reshape(4, 5).astype(np.float32)
+    # 14: rows 116..120, columns 1..4: 19 valid pixels whose median is 571.5; the row's nelec_per_nmgy is 512, the sky under the
+    # source 566.5 / 512, so that claimed + 5 is 571.5 exactly
+    v = (571.5 + np.concatenate([-3.0 - np.arange(9), [0.0], 3.0 + np.arange(9), [np.nan]])).astype(np.float32)
+    img.pixels[115:120, 0:4] = v.reshape(5, 4)
+    img.nelec_per_nmgy = img.nelec_per_nmgy.copy()
+    img.nelec_per_nmgy[119] = 512.0
+    img.sky[119, 0] = np.float32(566.5 / 512.0)
+    # 15: row 100 has 1.05 times the nelec_per_nmgy of row 30, and the source lies in column 30
+    img.nelec_per_nmgy[99] *= np.float32(1.05)
     pos += [(rng.uniform(-20.0, 140.0), rng.uniform(-20.0, 150.0)) for _ in range(64)]
     cat = [_ce(p) for p in pos]
     from celeste_jl_amd.model import box_around_point, clamp_box, julia_round
@@ -292,8 +327,21 @@ def sky_scene():
         h, w = julia_round(pc[0]), julia_round(pc[1])
         target = (med - 5.0) * (1.0 + sign * 4.0e-6)
         img.sky[h - 1, w - 1] = np.float32(target / float(img.nelec_per_nmgy[h - 1]))
+    img.sky[0, 129] = np.float32((claimed + 2.0) / float(img.nelec_per_nmgy[0]))          # 13: claimed + 5 = claimed_0 + 7
     want = [infer.bad_sky(ce, images) for ce in cat]
     assert want[11] is True and want[12] is False and want[8] is False and want[9] is False
+    # the three hand-made cases hold what they were made for
+    px13, box13 = valid_pixels(cat[13])
+    lo, hi = np.sort(px13)[[9, 10]]
+    c13 = float(img.sky[0, 129]) * float(img.nelec_per_nmgy[0]) + 5
+    assert box13 == (1, 4, 126, 130) and px13.size == 20 and hi - lo == 20 and float((lo + hi) * np.float32(0.5)) < c13 < float(hi)
+    assert want[13] is False
+    px14, box14 = valid_pixels(cat[14])
+    assert box14 == (116, 120, 1, 4) and px14.size == 19 and float(np.median(px14)) == 571.5
+    assert float(img.sky[119, 0]) * float(img.nelec_per_nmgy[119]) + 5.0 == 571.5 and want[14] is False
+    med15 = float(np.median(valid_pixels(cat[15])[0]))
+    assert float(img.sky[99, 29]) * float(img.nelec_per_nmgy[29]) + 5 < med15 < float(img.sky[99, 29]) * float(img.nelec_per_nmgy[99]) + 5
+    assert want[15] is False
     assert 10 < sum(want) < len(want) - 10                         # both values occur among the random ones too
     return images, cat, want
 
