@@ -1,19 +1,20 @@
 """-m gpu: mutation tests of the parity suite (trap A2 / A4).
 
-The HIP library is rebuilt with one deliberate indexing bug at a time (tests/mutants/build_mutants.py,
+The HIP library is rebuilt with one deliberate indexing bug at a time (tests/mutation.py,
 -DCELESTE_MUTANT=k in csrc/elbo_kernels.h): iota read by column instead of by row, the sky plane read transposed,
 one star stamp for every patch.  On the variable-field golden (varying sky plane, per-row calibration, per-patch
 stamps: tests/golden/field_72x88_9src_variable.npz) every mutant must break parity with the committed oracle
 outputs; on a constant-template golden the first two cannot be seen at all -- which is exactly why round 1's
 fixtures, all constant, did not cover the trap."""
 import os
-import subprocess
 import sys
 
 import pytest
 
+from mutation import ROOT, SUITES, run_child
+
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+SUITE = SUITES["engine"]
 
 CHECK = r"""
 import json, sys, numpy as np
@@ -63,20 +64,16 @@ sys.exit(0 if worst <= 1.0 else 3)
 
 
 def _parity(lib_path, case, mode="both"):
-    env = dict(os.environ)
-    if lib_path:
-        env["CELESTE_MI355X_LIB"] = lib_path
-    out = subprocess.run([sys.executable, "-c", CHECK % {"root": ROOT}, case, mode], capture_output=True, text=True, env=env,
-                         timeout=600)
-    assert out.returncode in (0, 3), out.stderr[-2000:]
-    return out.returncode == 0, out.stdout.strip()
+    """CHECK in a child (tests/mutation.py's runner: exit status 0 or 3, anything else stops every later child)"""
+    status, text = run_child([sys.executable, "-c", CHECK % {"root": ROOT}, case, mode], SUITE,
+                             lib_path, "%s %s %s" % (os.path.basename(lib_path or "product"), case, mode), normal=(0, 3), timeout=600)
+    return status == 0, text.strip()
 
 
 @pytest.fixture(scope="module")
 def mutants():
-    sys.path.insert(0, os.path.join(ROOT, "tests", "mutants"))
-    import build_mutants
-    return build_mutants.build()
+    libs = SUITE.build()
+    return [libs["engine", macro, k] for macro, k, _ in SUITE.mutants]
 
 
 def test_product_library_holds_parity_on_both_goldens():

@@ -1,93 +1,29 @@
-"""Mutation tests of the resid library's parity suite, after tests/test_satellite_mutants.py.
+"""Mutation tests of the resid library's parity suite (tests/mutation.py has the catalogue and the mechanism).
 
-The library is rebuilt with one deliberate bug at a time (-DCELESTE_RESID_MUTANT=k; the head of csrc/resid/celeste_resid.hip
-lists them) into tests/mutants/ (git-ignored build artefacts), and the parity tests of tests/test_gpu_resid.py -- those that
-compare the device with the numpy restatement -- run against it in a child process, the mutant selected through
-CELESTE_MI355X_RESID_LIB.  A child that fails (exit status 1) has killed its mutant; one that passes shows a bug the suite cannot
-see.  Any other end of a child (a signal, its time limit, pytest's statuses 2 to 5) is an error of the harness, not a kill: the
-test fails with the child's tail and nothing more is started on the device.
-
-The catalogue test (not -m gpu) keeps MUTANTS and the `CELESTE_RESID_MUTANT == k` switches of the source in step."""
-import os
-import re
-import subprocess
-import sys
-import time
-
+CELESTE_RESID_MUTANT, 5 mutants; the head of csrc/resid/celeste_resid.hip lists them.  The selection is what compares the device
+with the numpy restatement in tests/test_gpu_resid.py: the frame model, the filter maps, the peak rule."""
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-DIR = os.path.join(ROOT, "celeste.jl_amd", "csrc", "resid")
-SOURCE = os.path.join(DIR, "celeste_resid.hip")
-OUT = os.path.join(ROOT, "tests", "mutants")
-MUTANTS = {1: "light_in_last_column", 2: "bitmap_ignored", 3: "phi_transposed", 4: "iota_by_column", 5: "tie_rule_not_strict"}
-# what compares the device with the restatement: the frame model, the filter maps, the peak rule
-SELECT = "frame_model or explicit_bitmaps or filter_maps or find_peaks"
-CHILD_TIMEOUT = 300        # seconds; a child needs a small fraction of it
-_ABNORMAL = []             # the first child that ended with neither 0 nor 1: nothing is started after it
+from mutation import SUITES
 
-
-def _path(k):
-    return os.path.join(OUT, "libceleste_resid_mutant_%d_%s.so" % (k, MUTANTS[k]))
+SUITE = SUITES["resid"]
 
 
 def test_catalogue_and_source_agree():
-    text = open(SOURCE).read()
-    found = {int(k) for k in re.findall(r"\bCELESTE_RESID_MUTANT\s*==\s*(\d+)", text)}
-    assert found == set(MUTANTS) and 0 not in found
-    head = text[:text.index("#ifndef CELESTE_RESID_MUTANT")]
-    for k in MUTANTS:
-        assert re.search(r"^//\s+%d = " % k, head, flags=re.M), k
-    assert len(set(MUTANTS.values())) == len(MUTANTS) and "CELESTE_CLIENT_MUTANT ==" not in text and "CELESTE_FIT_MUTANT" not in text
+    SUITE.check_catalogue()
 
 
 @pytest.fixture(scope="module")
 def mutants():
-    """the mutated libraries: the library's own command line (the product's), one -D"""
-    sys.path.insert(0, ROOT)
-    import __graft_entry__ as ge
-    newest = max(os.path.getmtime(s) for s in ge.sources("resid"))
-    stale = [k for k in MUTANTS if not os.path.exists(_path(k)) or os.path.getmtime(_path(k)) < newest]
-    cmds = [ge.compile_command("resid", out=_path(k), defines=["CELESTE_RESID_MUTANT=%d" % k]) for k in stale]
-    procs = [subprocess.Popen(argv, cwd=cwd) for argv, cwd in cmds]
-    if [p.wait() for p in procs].count(0) != len(procs):
-        pytest.fail("a mutant did not build")
-    return {k: _path(k) for k in MUTANTS}
-
-
-def _child(lib_path, what):
-    """runs the parity tests in a child; (exit status, output).  Refuses once a child has ended abnormally."""
-    if _ABNORMAL:
-        pytest.fail("not started: an earlier child ended abnormally (%s)" % _ABNORMAL[0])
-    env = dict(os.environ)
-    env.pop("CELESTE_MI355X_RESID_LIB", None)
-    if lib_path:
-        env["CELESTE_MI355X_RESID_LIB"] = lib_path
-    cmd = [sys.executable, "-m", "pytest", "tests/test_gpu_resid.py", "-q", "-x", "-p", "no:cacheprovider", "-k", SELECT]
-    t0 = time.time()
-    try:
-        out = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=CHILD_TIMEOUT)
-        status, text = out.returncode, out.stdout + out.stderr
-    except subprocess.TimeoutExpired as e:
-        status = "time limit of %d s" % CHILD_TIMEOUT
-        text = "".join(x.decode(errors="replace") if isinstance(x, bytes) else (x or "") for x in (e.stdout, e.stderr))
-    failed = re.findall(r"^FAILED (\S+)", text, flags=re.M)
-    print("%s: status %s in %.1f s%s" % (what, status, time.time() - t0, (", failed " + failed[0]) if failed else ""))
-    if status not in (0, 1):
-        _ABNORMAL.append("%s: %s" % (what, status))
-        pytest.fail("the child of %s ended with %s, neither passed nor failed:\n%s" % (what, status, text[-3000:]))
-    return status, text
+    return SUITE.build()
 
 
 @pytest.mark.gpu
 def test_product_library_passes_the_selection():
-    status, text = _child(None, "product")
-    assert status == 0, text[-3000:]
-    assert re.search(r"\b\d+ passed", text) and "skipped" not in text.splitlines()[-1], text[-500:]
+    SUITE.product_passes()
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("k", sorted(MUTANTS), ids=lambda k: "%d-%s" % (k, MUTANTS[k]))
+@SUITE.each_mutant
 def test_mutant_is_killed_by_the_parity_tests(mutants, k):
-    status, text = _child(mutants[k], "mutant %d %s" % (k, MUTANTS[k]))
-    assert status == 1, "the mutated library still passes its parity tests: the fixture has no power against this bug"
+    SUITE.mutant_is_killed(mutants, k)

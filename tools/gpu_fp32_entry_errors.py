@@ -6,7 +6,7 @@ tests/test_gpu_parity.py rest on.  Needs the GPU.
 The suite's own fp32 test bodies are run with assert_fp32_parity replaced by a recorder (and the two variant bounds lifted),
 so that what is measured is exactly what the tests compare: the fp32 fuzz seeds, test_fp32_component_loop_within_1e4's
 field, the 2 x 2 and 2 x 4 (configs[4]) multifields, the variable fields, the randomised fuzz; then the two goldens against
-their committed oracle outputs, and the mutant libraries of tests/mutants (built beforehand) through test_mutants.CHECK.
+their committed oracle outputs, and the mutant libraries of tests/mutants (built beforehand: tests/mutation.py) through test_mutants.CHECK.
 
 For each fixture and parameter block (position, star / galaxy flux, colour, shape, type, k) it records the 50th / 99th /
 100th percentile of the ratio |fp32 - fp64| / scale for several floors F, and the old norm-scaled errors.
@@ -163,10 +163,10 @@ def measure(runs, failures, mut, tm):
             recorder((v, d, h), (z["v7"], z["d7"], z["h7"]), z["h7"], "golden %s flags %d" % (case, flags))
         ctx.close()
     if "--no-mutants" not in sys.argv:
-        sys.path.insert(0, os.path.join(ROOT, "tests", "mutants"))
-        import build_mutants
+        import mutation
+        engine = mutation.SUITES["engine"]
         libs = {0: None}
-        libs.update({k: build_mutants.path(k) for k in build_mutants.MUTANTS})
+        libs.update({k: engine.path(macro, k) for macro, k, _ in engine.mutants})
         for k, lib in libs.items():
             for case in ("field_72x88_9src_variable", "field_64x80_8src_nan"):
                 env = dict(os.environ)
