@@ -1,7 +1,8 @@
 // celeste_blend.hip -- libceleste_blend.so: maximize! with several active sources (include/celeste_blend.h).
 //
-// The engine's context and evaluation code (celeste_abi.hip) is compiled into this library, unchanged; the context with its
-// device buffers is engine_client.h's; this file adds the blend driver and two kernels of its own.  Per Newton iteration, for every live blend of the call at once:
+// The engine's context and its evaluation launcher (engine_eval.h: launch_eval, launch_cross, optim_config) are compiled into
+// this library, unchanged -- not the engine's host ABI, its optimiser or its device groups, so no RCCL; the context with its
+// device buffers is engine_client.h's; this file adds the blend driver and four kernels of its own.  Per Newton iteration, for every live blend of the call at once:
 //   launch_eval (MULTI)        the members of all live blends as one target list; every member's pixel sums with the
 //                              multi-active rule "an earlier active source visits this pixel" (elbo_kernels.h).  The
 //                              refusal rule (no member is a neighbour of a member of another blend) means a member's
@@ -15,7 +16,7 @@
 //                              celeste_maximize_batch, and the next trial point written into the table.
 // The (44 Sa)^2 blocks and the (41 Sa)^2 free Hessians stay in HBM; the host waits once per iteration for the blends'
 // phases.  No floating-point atomics: every sum runs in a fixed order.
-#include "../celeste_abi.hip"
+#include "../engine_eval.h"
 #include "../engine_client.h"
 #include "../../../include/celeste_blend.h"
 
@@ -527,11 +528,6 @@ struct BlendPlan {
     std::vector<std::vector<int32_t>> pair_src;    // per blend: (source a, source b) of each pair, in the cross kernels' order
 };
 
-static bool bl_lists(const celeste_ctx_t *c, int s, int t) {
-    for (int64_t q = c->h_nbr_off[s]; q < c->h_nbr_off[s + 1]; ++q) if (c->h_nbr_idx[q] == t) return true;
-    return false;
-}
-
 static int bl_plan(const celeste_ctx_t *c, int32_t n_blends, const int64_t *off, const int32_t *src, bool want_pairs,
                    BlendPlan &P) {
     if (n_blends < 0 || (n_blends > 0 && (!off || !src)) || (n_blends > 0 && off[0] != 0)) return CELESTE_ERR_INVALID_ARG;
@@ -568,8 +564,8 @@ static int bl_plan(const celeste_ctx_t *c, int32_t n_blends, const int64_t *off,
             for (int ia = 0; ia < P.sa[b]; ++ia)
                 for (int ib = ia + 1; ib < P.sa[b]; ++ib) {
                     const int sA = src[P.m0[b] + ia], sB = src[P.m0[b] + ib];
-                    if (bl_lists(c, sA, sB)) { P.pairs[b].push_back({ia, ib}); P.pair_src[b].push_back(sA); P.pair_src[b].push_back(sB); }
-                    else if (bl_lists(c, sB, sA)) { P.pairs[b].push_back({ib, ia}); P.pair_src[b].push_back(sB); P.pair_src[b].push_back(sA); }
+                    if (nbr_lists(c, sA, sB)) { P.pairs[b].push_back({ia, ib}); P.pair_src[b].push_back(sA); P.pair_src[b].push_back(sB); }
+                    else if (nbr_lists(c, sB, sA)) { P.pairs[b].push_back({ib, ia}); P.pair_src[b].push_back(sB); P.pair_src[b].push_back(sA); }
                 }
     return CELESTE_OK;
 }
@@ -630,11 +626,7 @@ static int bl_eval_launch(celeste_blend_ctx_t *bc, const double *d_table, const 
         HIP_TRY(hipMemcpyAsync(o.pairs, pairs.data(), np * sizeof(BlendPair), hipMemcpyHostToDevice, c->stream));
         HIP_TRY(hipMemcpyAsync(d_pa, psa.data(), np * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
         HIP_TRY(hipMemcpyAsync(d_pb, psb.data(), np * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
-        hipLaunchKernelGGL(cross_kernel, dim3((unsigned)(np * c->N)), dim3(64), 0, c->stream, c->d_images, c->d_patches,
-                           c->d_coefs, c->d_bitmaps, c->d_srcimg, c->d_comps, c->d_nbr_off, c->d_nbr_idx, c->d_val_off,
-                           c->d_val, d_pa, d_pb, c->N, c->NC, d_rec, c->d_vis_off, c->d_vis_img, (int)c->dense);
-        hipLaunchKernelGGL(cross_lift_kernel, dim3((unsigned)np), dim3(256), 0, c->stream, d_table, c->d_images, c->d_patches,
-                           c->d_geo, d_pa, d_pb, d_rec, c->N, o.x, c->d_vis_off, c->d_vis_img, (int)c->dense);
+        launch_cross(c, d_table, np, d_pa, d_pb, d_rec, o.x, c->stream);
         HIP_TRY(hipGetLastError());
     }
     return CELESTE_OK;

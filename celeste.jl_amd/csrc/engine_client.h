@@ -1,6 +1,6 @@
 // engine_client.h -- what the libraries that compile the engine's context into themselves (blend, fit, phot, info, resid, astrom) share.
 //
-// Included right after engine_context.h (blend: after celeste_abi.hip, which includes it), whose celeste_ctx, HIP_TRY, Comp, SrcImg, DevPatch, table_entry ... it uses; the engine
+// Included right after engine_context.h (blend: after engine_eval.h, which includes it), whose celeste_ctx, HIP_TRY, Comp, SrcImg, DevPatch, table_entry ... it uses; the engine
 // does not include it.  Everything here is static or __device__ __forceinline__: no library's export map knows of it.
 //   host    a context base (engine context, growable device buffers, stage events, stage times) with its create and destroy,
 //           the status fold; for the libraries that walk pixel visits (fit, phot, info): the target check, the prep_kernel

@@ -2,9 +2,10 @@
 //
 // Owns the device copies of the problem (images, patches, spline coefficients, neighbour graph), the stream and
 // page-locked pools and the upload arena, and defines celeste_images_create / celeste_ctx_create[_on] / celeste_ctx_destroy.
-// celeste_abi.hip (the engine, and the blend library through it) includes it under its evaluation and optimiser code;
-// the fit, phot, info, resid and astrom libraries include it alone, followed by engine_client.h.  Nothing here evaluates
-// the ELBO: a context's evaluation and optimiser buffers are plain pointers that only celeste_abi.hip fills.
+// engine_eval.h (the evaluation launcher: the engine's celeste_abi.hip and the blend library) includes it under the kernels
+// it launches; the fit, phot, info, resid and astrom libraries include it alone, followed by engine_client.h.  Nothing here
+// evaluates the ELBO: a context's evaluation and optimiser buffers are plain pointers that only engine_eval.h and
+// celeste_abi.hip fill.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <algorithm>

@@ -31,7 +31,7 @@ ABNORMAL = []              # the first child that ended abnormally, of whichever
 
 # macro -> the files under csrc that carry its switches; the first one's head defines it
 SOURCES = {
-    "CELESTE_MUTANT": ["elbo_kernels.h", "fused_kernels.h"],
+    "CELESTE_MUTANT": ["elbo_kernels.h", "fused_kernels.h", "eval_fused.h"],
     "CELESTE_CLIENT_MUTANT": ["engine_client.h"],
     "CELESTE_FIT_MUTANT": ["fit/celeste_fit.hip"],
     "CELESTE_PHOT_MUTANT": ["phot/celeste_phot.hip"],

@@ -1,7 +1,8 @@
 """CPU: the build table of __graft_entry__.py (LIBRARIES) against the tree and against what it builds: every entry names
-files that exist, the table's directories are the directories of csrc/ that hold a .hip file, and the five libraries that
-compile the engine's context without its evaluation code (fit, phot, info, resid, astrom) export their header's functions
-and nothing else, and ask no library for an RCCL symbol."""
+files that exist, the table's directories are the directories of csrc/ that hold a .hip file, only the engine compiles a
+.hip file of csrc's top level and links RCCL, and the five libraries that compile the engine's context without its
+evaluation code (fit, phot, info, resid, astrom) and the one that compiles it with the evaluation launcher (blend) export
+their header's functions and nothing else, and ask no library for an RCCL symbol."""
 import importlib
 import os
 import re
@@ -44,18 +45,24 @@ def test_the_table_lists_every_directory_of_csrc_that_holds_a_hip_file():
     assert have == {e["dir"] for e in g.LIBRARIES.values()}, have ^ {e["dir"] for e in g.LIBRARIES.values()}
 
 
-def test_only_the_engine_and_blend_compile_the_engine_whole_and_link_rccl():
+def test_only_the_engine_compiles_the_engine_whole_and_links_rccl():
     import __graft_entry__ as g
     for name, e in g.LIBRARIES.items():
-        whole = name in ("engine", "blend")
-        assert (e["csrc"] == "all") == whole and ("-lrccl" in e["link"]) == whole, name
+        assert (e["csrc"] == "all") == (name == "engine") and ("-lrccl" in e["link"]) == (name == "engine"), name
         text = open(e["source"]).read()
-        assert ('#include "../celeste_abi.hip"' in text) == (name == "blend"), name
         if name in CONTEXT_ONLY:
             assert '#include "../engine_context.h"\n#include "../engine_client.h"\n' in text and e["link"] == ["-lpthread"], name
+        if name == "blend":
+            assert '#include "../engine_eval.h"\n#include "../engine_client.h"\n' in text and e["link"] == ["-lpthread"], name
+    # no file under csrc includes a .hip file: a library compiles its own and headers
+    for d, _, files in os.walk(g.CSRC):
+        for f in files:
+            if f.endswith((".hip", ".h", ".inc")):
+                included = re.findall(r'^\s*#\s*include\s*[<"]([^>"]+)[>"]', open(os.path.join(d, f)).read(), flags=re.M)
+                assert not [i for i in included if i.endswith(".hip")], (d, f)
 
 
-@pytest.mark.parametrize("name", CONTEXT_ONLY)
+@pytest.mark.parametrize("name", CONTEXT_ONLY + ("blend",))
 def test_a_context_only_library_exports_its_header_and_imports_no_rccl_symbol(g, name):
     e = g.LIBRARIES[name]
     module = importlib.import_module("celeste_jl_amd." + e["module"])

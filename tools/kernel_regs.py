@@ -1,7 +1,7 @@
 """Registers / scratch / LDS of every kernel in the compiled library, and VALU / LDS / FP64 instruction counts of the
 pixel kernel's loops (static, from the ISA; no GPU needed).  usage: python tools/kernel_regs.py [name-filter [source]]
-source: a .hip file under csrc/ of a library that compiles the engine into itself, e.g. info/celeste_info.hip (default:
-celeste_abi.hip)"""
+source: a .hip file under csrc/ of a library that compiles the engine's headers into itself, e.g. info/celeste_info.hip or
+blend/celeste_blend.hip (default: the engine, celeste_abi.hip)"""
 import os
 import re
 import subprocess
